@@ -8,9 +8,14 @@ streams x 16 UDP subscribers on one MI355X).  With N ranks the global session se
 N x 1024 streams sharded by FNV-1a(stream ID) with no collective on the data path (weak
 scaling); ``--subs 64`` gives the C3 per-GPU shape.
 
-All W+K input batches are generated and made resident in HBM before timing.  Launch::
+The input batches are generated and made resident in HBM before timing (one per step while they
+fit ``--resident-gb``; past that the resident batches are replayed in order, their arrival times
+moved on by the replayed span).  A plain run sets up, warms up, times the K steps and prints the
+result line; ``--full`` adds what takes runs of its own (the ingest / keyframe / plan durations
+from extra steps with every timing event, the CPU baselines, at N > 1 the replicas' check), and
+``--dump-outputs DIR`` writes what the last timed step's fan-out returned.  Launch::
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 """
 from __future__ import annotations
@@ -128,7 +133,78 @@ def run_step(ctx: edgpu.Context, bt: dict, link=None):
     ctx.keyframe_index()
     if link is not None:                # N > 1: this rank's images to its replicas' ranks, and back
         link.sync(bt["t"])
-    ctx.fanout(bt["t"])
+    return ctx.fanout(bt["t"])
+
+
+def batch_footprint(bt: dict) -> int:
+    """HBM bytes one resident batch holds."""
+    return int(bt.get("raw_bytes", bt["bytes"])) + 16 * bt["n"]
+
+
+def later_batch(ctx, bt: dict, ms: int) -> dict:
+    """The resident batch `bt` as a step `ms` later: the same packets (blob, segments) with every
+    arrival time and the tick's end moved on by `ms`.  Only the 16-byte descriptors (or the TCP
+    read rows) are copied; built outside the timing."""
+    nb = dict(bt)
+    nb["t"] = bt["t"] + ms
+    if "tcp" in bt:
+        reads = bt["tcp"]["reads"].copy()
+        reads["arrival_ms"] += ms
+        nb["tcp"] = dict(bt["tcp"], reads=reads)
+        return nb
+    d = bt["desc"].clone()
+    d.view(torch.int64).view(-1, 2)[:, 1] += ms          # PKT_DTYPE: arrival_ms is the second 8 bytes
+    nb["desc"] = d
+    if "pinned" in bt:
+        a = d.cpu().numpy()
+        hb = ctx.host_alloc(a.nbytes)
+        hb.array[:] = a
+        nb["pinned"] = dict(bt["pinned"], desc=hb)
+    return nb
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(ctx: edgpu.Context, r, path: str, prefix: str = "", seed: int = 0xEA5D):
+    """What the caller of the last timed step's edgpu_fanout received (the result's sub-stream table,
+    output descriptors and arena), as <path>/<prefix><name>.npy: the whole sub-stream table, totals
+    over every descriptor, and a fixed seeded sample of descriptors and of whole output packets
+    (the outputs of a C2 step are 8 GB).  The sample depends only on the descriptor count."""
+    os.makedirs(path, exist_ok=True)
+    st = ctx.stats()
+    npk, nsub = int(st.pass_packets), int(r.n_substreams)
+    subs = ctx.copy_to_host(r.substreams, nsub * edgpu.SUB_DTYPE.itemsize).view(edgpu.SUB_DTYPE)
+    desc = ctx.copy_to_host(r.desc, npk * edgpu.OUT_DTYPE.itemsize).view(edgpu.OUT_DTYPE)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    out = {}
+    out["tick_stats"] = np.array([st.relayed_packets, st.relayed_bytes, st.arena_bytes, st.pass_packets,
+                                  st.pass_arena_bytes, nsub, st.status], dtype=np.float64)
+    rows = np.sort(rng.choice(nsub, min(nsub, 65536), replace=False)) if nsub else np.zeros(0, np.int64)
+    out["substreams"] = np.stack([rows.astype(np.float64)] + [subs[k][rows].astype(np.float64) for k in
+                                 ("subscriber", "track", "kind", "transport", "desc_base", "desc_count",
+                                  "out_base", "out_bytes", "sender", "flags")], axis=1)
+    out["desc_totals"] = np.array([npk, desc["len"].sum(dtype=np.float64), desc["offset"].sum(dtype=np.float64),
+                                   desc["packet_id"].sum(dtype=np.float64)], dtype=np.float64)
+    pick = np.sort(rng.choice(npk, min(npk, 262144), replace=False)) if npk else np.zeros(0, np.int64)
+    out["desc_sample"] = np.stack([pick.astype(np.float64)] + [desc[k][pick].astype(np.float64)
+                                  for k in ("offset", "len", "packet_id")], axis=1)
+    # whole packets: the arena bytes of every 64th sampled descriptor, one row each, padded with -1
+    pk = pick[::64]
+    width = int(desc["len"][pk].max()) if len(pk) else 0
+    pkts = np.full((len(pk), width), -1.0, dtype=np.float32)
+    for i, k in enumerate(pk.tolist()):
+        off, ln = int(desc["offset"][k]), int(desc["len"][k])
+        if ln and off + ln <= st.pass_arena_bytes:
+            pkts[i, :ln] = ctx.copy_to_host(r.arena + off, ln)
+    out["packet_index"] = pk.astype(np.float64)
+    out["packet_bytes"] = pkts
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed {DUMP_MAX_BYTES}")
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{prefix}{name}.npy"), a)
+    return {"dir": path, "arrays": sorted(out), "bytes": total}
 
 
 def replica_preflight(ctx, world: int, rank: int) -> dict:
@@ -498,7 +574,19 @@ def main():
     ap.add_argument("--sessions", type=int, default=1024, help="sessions per GPU")
     ap.add_argument("--subs", type=int, default=16, help="UDP subscribers per session")
     ap.add_argument("--tick-ms", type=int, default=1000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: --timing-steps steps after the timed ones with every "
+                         "timing event (the ingest, keyframe and plan durations), the CPU baselines (the "
+                         "reference reflector and the restatement on the same workload) and, at N > 1, the "
+                         "replicas' check against their owners; a plain run leaves those fields null")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one's fan-out returned (sub-stream table, "
+                         "descriptor totals, a fixed seeded sample of descriptors and output packets) as "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MB")
+    ap.add_argument("--resident-gb", type=float, default=64.0,
+                    help="HBM for resident input batches: steps past what fits replay the resident batches in "
+                         "order, their arrival times moved on (config.input_batches in the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--ingest", choices=["desc", "tcp", "host"], default="desc",
                     help="desc: packets handed over as descriptors + slots in HBM (edgpu_ingest, the "
                          "reflector's per-packet PushPacket boundary); tcp: the pushers' RTSP-interleaved TCP "
@@ -512,8 +600,8 @@ def main():
                     help="per-output rewrite stage on every subscriber (seq/ts deltas + SSRC override, "
                          "edgpu_subscriber_rewrite); the reference's parity mode is the identity (default)")
     ap.add_argument("--timing-steps", type=int, default=3,
-                    help="steps after the timed region that record every timing event (the ingest, "
-                         "keyframe and plan durations of the line)")
+                    help="with --full: steps after the timed region that record every timing event (the "
+                         "ingest, keyframe and plan durations of the line)")
     ap.add_argument("--all-timing-events", action="store_true",
                     help="record every timing event inside the timed steps too (the ingest / keyframe / "
                          "plan durations then come from them; each event costs the step 4-8 us)")
@@ -570,13 +658,16 @@ def main():
     gids = owned_sessions(args.sessions, rank, world) if world > 1 else np.arange(args.sessions)
     fleet = H264Fleet(gids, tick_ms=args.tick_ms)
     steps, warm = args.steps, args.warmup
-    extra = 0 if args.all_timing_events else args.timing_steps
-    log(f"[bench] rank {rank}/{world}: {len(gids)} sessions x {args.subs} subs, generating {steps + warm + extra} batches")
+    extra = args.timing_steps if args.full and not args.all_timing_events else 0
+    need = steps + warm + extra
+    log(f"[bench] rank {rank}/{world}: {len(gids)} sessions x {args.subs} subs, generating up to {need} batches")
     t_gen = time.time()
     gen = torch.Generator(device=dev)
     gen.manual_seed(0xEA5D + rank)
-    batches = []
-    for _ in range(steps + warm + extra):
+    batches, resident = [], 0          # the resident batches (the steps' inputs follow below)
+    for _ in range(need):
+        if batches and resident + batch_footprint(batches[-1]) > args.resident_gb * 2**30:
+            break
         b = fleet.next_batch()
         bt = make_batch_on_device(b, dev, gen)
         if args.ingest == "tcp":
@@ -584,8 +675,9 @@ def main():
             bt.pop("blob")
             bt["raw_bytes"] = bt["tcp"]["raw_bytes"]
         batches.append(bt)
+        resident += batch_footprint(bt)
     torch.cuda.synchronize(dev)
-    log(f"[bench] generated in {time.time() - t_gen:.1f}s; max batch {max(b['n'] for b in batches)} pkts, "
+    log(f"[bench] {len(batches)} generated in {time.time() - t_gen:.1f}s; max batch {max(b['n'] for b in batches)} pkts, "
         f"{max(b['bytes'] for b in batches) / 2**20:.0f} MiB")
 
     # Output capacity per tick: every subscriber gets at most the packets of one batch (the
@@ -605,6 +697,10 @@ def main():
             bt["pinned"] = make_pinned(ctx, bt)
             bt.pop("blob")
         torch.cuda.empty_cache()
+    # one input per step: the resident batches, then the same again a whole span later, and so on
+    n_res = len(batches)
+    batches = [batches[i] if i < n_res else later_batch(ctx, batches[i % n_res], (i // n_res) * n_res * args.tick_ms)
+               for i in range(need)]
     for si, _ in enumerate(gids):
         s = ctx.session_add(fleet.sdp())
         for _k in range(args.subs):
@@ -642,7 +738,7 @@ def main():
     # The timed steps record only the fan-out copy kernel's event pair (the roofline's duration):
     # every event is a marker the stream waits on, 4-8 us of idle GPU each
     # (profiles/r03ak_timing_events_ab/).  The ingest / keyframe / plan durations come from
-    # `extra` steps after the timed region, with every event recorded.
+    # `extra` steps after the timed region, with every event recorded (--full).
     ctx.set_timing(ctx.TIMING_ALL if args.all_timing_events else ctx.TIMING_FANOUT)
 
     if dist:
@@ -651,8 +747,9 @@ def main():
     x0 = (link.sync_s, link.bytes_sent, sum(mb.wait_s for mb, _ in list(link.out.values()) + list(link.inbox.values()))) \
         if link else None
     t0 = time.perf_counter()
+    last = None
     for i in range(warm, warm + steps):
-        run_step(ctx, batches[i], link)
+        last = run_step(ctx, batches[i], link)
     ctx.sync()
     torch.cuda.synchronize(dev)
     if dist:
@@ -666,6 +763,9 @@ def main():
     if st.status != 0:
         raise SystemExit(f"engine status {st.status}")
     k_fan = ctx.kernel_times(0)
+    dumped = None
+    if args.dump_outputs and last is not None:
+        dumped = dump_outputs(ctx, last, args.dump_outputs, prefix=f"rank{rank}_" if world > 1 else "")
     if extra:
         ctx.set_timing(ctx.TIMING_ALL)
         for i in range(warm + steps, warm + steps + extra):
@@ -696,7 +796,8 @@ def main():
             def check():
                 torch.cuda.set_device(local)          # (a thread of its own: HIP's device is per thread)
                 return replica_check(ctx, link, gids, world)
-            xdev, hung = run_bounded(check, 120.0)
+            if args.full:
+                xdev, hung = run_bounded(check, 120.0)
             if not hung:
                 per = [None] * world
                 dist.all_gather_object(per, ((x1[0] - x0[0]) / steps, (x1[1] - x0[1]) / steps, (x1[2] - x0[2]) / steps))
@@ -765,19 +866,20 @@ def main():
     slot_b = float(np.mean([bt["bytes"] for bt in timed]))
     read_b = float(np.mean([bt["raw_bytes"] for bt in timed])) if args.ingest == "tcp" else slot_b + 16 * npk
     ing_alg = read_b + slot_b + 32 * npk
-    ing_ms = float(np.mean(k_ing)) if k_ing else float("nan")
-    ing_ach = ing_alg / (ing_ms / 1e3) / 1e9
+    ing_ms = float(np.mean(k_ing)) if k_ing else None      # (timed in the --full steps)
+    ing_ach = ing_alg / (ing_ms / 1e3) / 1e9 if k_ing else None
     ingest = {"kernels": "k_ingest + k_tcp_* deframe" if args.ingest == "tcp" else "k_ingest",
               # HIP events on the context stream: with RTSP-interleaved reads the deframe kernels
               # run on a second stream beside the previous tick's fan-out (the host reads their
               # report, then enqueues k_ingest), so this is the time the ingest adds to the step
               "timing": ("exposed: the deframe runs beside the previous tick's fan-out; the context stream "
                          "sees k_ingest" if args.ingest == "tcp" else "k_ingest launch duration"),
-              "alg_bytes_per_launch": int(ing_alg), "avg_ms": round(ing_ms, 4), "achieved": round(ing_ach, 1),
-              "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ing_ach / HBM_PEAK_GBS, 4),
+              "alg_bytes_per_launch": int(ing_alg), "avg_ms": round(ing_ms, 4) if k_ing else None,
+              "achieved": round(ing_ach, 1) if k_ing else None,
+              "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ing_ach / HBM_PEAK_GBS, 4) if k_ing else None,
               "traffic": ing_traffic, "traffic_source": traffic_source if ing_traffic else None}
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline_reference(args)
         if cpu is None:             # no reference build travelled with the tree: the restatement
             cpu = cpu_baseline(args)
@@ -802,6 +904,8 @@ def main():
                    **({"deframe_walk": deframe_walk} if deframe_walk else {}),
                    "sessions_per_gpu": args.sessions, "subs_per_session": args.subs,
                    "tick_ms": args.tick_ms,
+                   "input_batches": {"resident": n_res, "replayed_with_later_arrivals": need > n_res},
+                   "full": args.full,
                    "rewrite": rewrite_desc,
                    "engine_env": knobs,
                    **({"diagnostic_rings": {"video_ring_mb": args.ring_mb, "growth": not args.no_ring_growth}}
@@ -829,7 +933,7 @@ def main():
         "per_step": per_step,
         "timing_events": ("every kernel's, inside the timed steps" if args.all_timing_events else
                           f"the fan-out copy kernel's pair inside the timed steps; ingest, keyframe and plan "
-                          f"from {extra} steps after them"),
+                          + (f"from {extra} steps after them" if extra else "durations only with --full")),
         "ingest": ingest,
         "cpu_baseline": cpu,
         # the metric counts packets made send-ready in HBM; what reaches sockets is host-bound
@@ -839,6 +943,8 @@ def main():
                       "and 7.1-7.9 M in reference-exact one-datagram-per-send mode, 0.85-1.00x the reference's "
                       "sendto() path on the same box (profiles/r05z_wire/, DESIGN.md 5.6)"),
     }
+    if dumped is not None:
+        res["dumped_outputs"] = dumped
     if rep is not None:
         res["replicas"] = rep
     elif xdev is not None:

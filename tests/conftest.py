@@ -32,6 +32,11 @@ def udp_port_lock():
     """tools/qtss_replay binds the traces' fixed loopback source ports for UDP pushers: runs of it
     on the CPU take turns under pytest -n (one machine-wide lock file)."""
     import fcntl
-    with open(os.path.join(tempfile.gettempdir(), "edgpu_udp_ports.lock"), "a+") as lk:
+    path = os.path.join(tempfile.gettempdir(), "edgpu_udp_ports.lock")
+    try:
+        lk = open(path, "a+")
+    except PermissionError:                # another user's runs made it: flock works on a read-only one
+        lk = open(path, "r")
+    with lk:
         fcntl.flock(lk, fcntl.LOCK_EX)
         yield

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/${1:-ticks}
 mkdir -p $OUT
 for T in 100 20; do
     S=$((10000 / T)); W=$((3000 / T))
-    ARGS="--tick-ms $T --steps $S --warmup $W --no-cpu-baseline"
+    ARGS="--tick-ms $T --steps $S --warmup $W --full --no-cpu-baseline"
     timeout -k 10 300 python3 $R/bench.py $ARGS > $OUT/bench_t$T.json 2> $OUT/bench_t$T.err
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d $OUT/kt$T -o kt -- python3 $R/bench.py $ARGS > $OUT/kt_bench_t$T.json 2> $OUT/kt_bench_t$T.err
 done
