@@ -553,7 +553,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
         // bytes << 20) per sender in registers (wave_inclusive_scan_u64), the wave totals meet in
         // LDS across one barrier.  A packet keeps the prefixes of its own sender and of its track's
         // other one (RTP / RTCP, ls ^ 1): its rank in the track (fStreamCountID order) is their sum.
-        // (a packet refused after SPEC's guess, !a with sbytes > 0, still counts its hole's bytes)
+        // (only packets with slot bytes count: SPEC's recopy passes a refused packet 0, so its hole closes)
         auto rank_scan = [&](bool a, bool z, uint32_t sbytes) {
             const int lane = tid & 63, wid = tid >> 6;
             const uint64_t mx = (a ? 1ull | (uint64_t)(z ? 1 : 0) << 10 : 0ull) | (uint64_t)sbytes << 20;
@@ -741,24 +741,24 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
         const bool nz = acc && len > 0;
         const uint32_t slotb = nz ? ((len + 4 + 15) & ~15u) : 0;
         // ---- per-sender queue index / slot offset / non-empty count (rank_scan above).  SPEC:
-        // the slot bytes stay the guessed ones (a refused packet's bytes become a hole), and the
-        // ranks are scanned again only if a packet's enqueue / non-empty state differs from the guess
-        bool recopied = false;
+        // the ranks are scanned again only if a packet's enqueue / non-empty state or its length
+        // differs from the guess
         if constexpr (SPEC) {
-            if (__syncthreads_or(acc != acc0 || nz != acc0 ? 1 : 0)) {
-                // a refusal: the round is laid out again without the refused packets' bytes and its
-                // enqueued packets copied again to their final places (from the batch, so the two
-                // copies never read each other).  The guessed layout's end stays as the sender's
+            if (__syncthreads_or(acc != acc0 || nz != acc0 || len != len_d ? 1 : 0)) {
+                // a refusal or a stripped receive-time trailer: the round is laid out again without
+                // the refused packets' bytes, every slot sized from its final length (the layout the
+                // header-first path gives: ring retention must not depend on which path ran), and
+                // its enqueued packets copied again to their final places (from the batch, so the
+                // two copies never read each other).  The guessed layout's end stays as the sender's
                 // write high-water mark (vclob): ring slots it reached are no longer intact.
                 if (tid < (int)nsnd) s_vclob[tid] = max(s_vclob[tid], s_vbyte[tid] + (c_tot[tid] >> 20));
-                const uint32_t fb = nz ? slotb_s : 0u;
+                const uint32_t fb = slotb;
                 rank_scan(acc, nz, fb);
                 p_slotb[tid] = fb;
                 p_vb[tid] = nz ? s_vbyte[ls] + my_slotpre : 0ull;
                 p_len[tid] = (uint16_t)len;
                 __syncthreads();
                 slot_copy(false);
-                recopied = true;
                 // (the header words and the arrival from LDS again, rather than held across the copy)
                 const u32x4 z4 = u32x4{0u, 0u, 0u, 0u};
                 const u32x4 w0 = acc0 ? p_hdr[tid][0] : z4, w1 = acc0 && len_d > 12 ? p_hdr[tid][1] : z4;
@@ -766,9 +766,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
                 hdr[4] = w1.y; hdr[5] = w1.z; hdr[6] = w1.w;
                 arrival = p_arr[tid];
             }
-            if (!recopied && nz && len != len_d)         // a stripped trailer: the slot header's length
-                reinterpret_cast<uint32_t*>(s_ring[ls])[(((s_vbyte[ls] + my_slotpre) >> 4) & s_wmask[ls]) * 4] =
-                    slot_header(len);
         } else {
             rank_scan(acc, nz, slotb);
         }
