@@ -150,8 +150,40 @@ struct StreamDev {
     uint64_t packet_count;          // ReflectorStream::fPacketCount (shared by both senders)
 };
 
+// Per-stream reception statistics (edgpu_stream_stats_*), indexed like StreamDev.  One wave of
+// k_stream_stats owns a row: it walks the track's RTP sender, then its RTCP sender, over the queue
+// indices enqueued since its last launch.  The RTP half is RFC 3550 A.1 / A.8 (update_seq without
+// probation, interarrival jitter scaled by 16); the bitrate state is ReflectorStream's
+// fBytesSentInThisInterval / fLastBitRateSample / fCurrentBitRate (ReflectorStream.h:503-505,
+// 542-557).  All zero while disabled.
+struct StatDev {                    // 192 B
+    uint32_t enabled, clock_rate;   // clock_rate 0: no jitter
+    uint32_t sender;                // the track's RTP sender (its RTCP sender follows it)
+    uint32_t _pad0;
+    // RTP sender
+    uint64_t head;                  // next queue index to examine
+    uint64_t packets, bytes;        // every packet with len > 0
+    uint64_t missed;                // packets that left the rings before they were examined
+    uint32_t short_packets;         // 0 < len < 12
+    uint32_t has_src, ssrc, ssrc_changes;
+    uint32_t base_seq, max_seq, cycles, bad_seq;
+    uint32_t received, misordered, restarts;
+    uint32_t has_transit, transit, jitter;
+    // RTCP sender
+    uint32_t sr_count, sr_rtp;
+    uint64_t rtcp_head, rtcp_packets, rtcp_bytes, rtcp_missed;
+    uint64_t sr_ntp;
+    int64_t  sr_arrival_ms;
+    uint32_t sr_packets, sr_octets;
+    // bitrate
+    uint32_t interval_bytes, bitrate;
+    int64_t  last_sample_ms;
+    uint64_t _pad1;
+};
+static_assert(sizeof(StatDev) == 192, "StatDev layout");
+
 struct SessionDev {
-    uint32_t first_sender;          // senders of track t: first_sender + 2t (+1 for RTCP)
+    uint32_t first_sender;         // senders of track t: first_sender + 2t (+1 for RTCP)
     uint32_t ntracks;
     uint32_t video_key_flag;        // ReflectorSession::fHasVideoKeyFrameUpdate
     uint32_t first_stream;

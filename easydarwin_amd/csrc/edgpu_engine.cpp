@@ -114,6 +114,19 @@ struct DevVec {
 
 struct TrackHost { uint32_t type = 0; std::string name; uint32_t track_id = 0; };   // type: 1 video, 2 audio
 
+// The RTP clock rate of an rtpmap payload name: the decimal digits after its first '/'
+// ("H264/90000", "MPEG4-GENERIC/44100/2"); 0 without a '/' or digits, or past 32 bits.
+static uint32_t rtpmap_clock_rate(const std::string& name) {
+    const size_t p = name.find('/');
+    if (p == std::string::npos) return 0;
+    uint64_t v = 0;
+    for (size_t i = p + 1; i < name.size() && name[i] >= '0' && name[i] <= '9'; i++) {
+        v = v * 10 + (uint64_t)(name[i] - '0');
+        if (v > 0xFFFFFFFFull) return 0;
+    }
+    return (uint32_t)v;
+}
+
 // A track's receiver-report state toward a UDP pusher (ReflectorStream fields
 // fReceiverReportBuffer / fDestRTCPAddr / fDestRTCPPort and the RTCP sender's fLastRRTime).
 struct SourceHost {
@@ -222,6 +235,8 @@ struct SessionHost {
     std::vector<SourceHost> src;    // per track
     bool alive = true;              // false after edgpu_session_remove (its id may be reused)
     std::vector<uint32_t> subs;     // attached subscriber handles
+    std::vector<uint32_t> clock_rate;   // per track (rtpmap_clock_rate)
+    bool stats = false;             // edgpu_stream_stats_enable
 };
 
 // RTCPSRPacket::GetACName (RTCPSRPacket.cpp:87-117): item type 1, length byte, "QTSS<secs>",
@@ -275,9 +290,11 @@ struct edgpu_ctx {
     bool kf_recorded = false;
     // per-launch timing history: [which][slot][start,end]
     static const int kHist = 256;
-    hipEvent_t hist[4][kHist][2] = {};
-    uint32_t hist_n[4] = {0, 0, 0, 0};      // pairs recorded (monotonic sequence numbers)
-    uint32_t hist_rd[4] = {0, 0, 0, 0};     // pairs already returned by edgpu_kernel_times
+    // (ring 4, the stream-statistics kernel: its events are created by the first
+    // edgpu_stream_stats_enable)
+    hipEvent_t hist[5][kHist][2] = {};
+    uint32_t hist_n[5] = {0, 0, 0, 0, 0};   // pairs recorded (monotonic sequence numbers)
+    uint32_t hist_rd[5] = {0, 0, 0, 0, 0};  // pairs already returned by edgpu_kernel_times
     // Borrowed end points.  A whole-tick entry (ring 1) ends at its copy kernel's end event
     // (ring 0 sequence number in tick_end[slot]); a keyframe entry (ring 3) starts at the end
     // event of the ingest it indexes (ring 2 sequence number in kf_from[slot]) when nothing ran
@@ -286,7 +303,7 @@ struct edgpu_ctx {
     static const uint32_t kOwnStart = 0xFFFFFFFFu;
     uint32_t tick_end[kHist] = {};
     uint32_t kf_from[kHist] = {};
-    uint32_t last_seq[4] = {0, 0, 0, 0};    // each ring's newest complete pair (edgpu_last_timings)
+    uint32_t last_seq[5] = {0, 0, 0, 0, 0}; // each ring's newest complete pair (edgpu_last_timings)
     bool kf_share = false;                  // the last ingest's end event may start the keyframe entry
     uint64_t fanout_launches = 0;
     int64_t last_now = 0;               // clock of the last edgpu_fanout (backpressure reports)
@@ -314,6 +331,8 @@ struct edgpu_ctx {
     DevVec<SessionDev> d_sessions;
     DevVec<SenderDev> d_senders;
     DevVec<StreamDev> d_streams;
+    DevVec<StatDev> d_stats;            // allocated by the first edgpu_stream_stats_enable; zero rows = disabled
+    uint32_t n_stats = 0;               // sessions with statistics enabled
     DevVec<SubDev> d_subs;
     DevVec<uint32_t> d_sub_index;
     DevVec<uint32_t> d_sub_range;
@@ -580,7 +599,7 @@ int edgpu_ctx_create(const edgpu_config* cfg_in, edgpu_ctx** out) {
     auto bad = [&](const char* what) { edgpu_ctx_destroy(x); return fail(EDGPU_OUT_OF_MEMORY, what); };
     if (hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking) != hipSuccess) return bad("stream");
     if (hipEventCreateWithFlags(&x->wd_ev, hipEventDisableTiming) != hipSuccess) return bad("watchdog event");
-    for (auto& w : x->hist) for (auto& s : w) for (auto& e : s) if (hipEventCreate(&e) != hipSuccess) return bad("event");
+    for (int w = 0; w < 4; w++) for (auto& s : x->hist[w]) for (auto& e : s) if (hipEventCreate(&e) != hipSuccess) return bad("event");
     if (dmalloc(&x->d_desc, sizeof(edgpu_pkt_desc) * (size_t)c.max_batch_packets) != hipSuccess) return bad("desc staging");
     if (dmalloc(&x->d_seg, sizeof(uint32_t) * ((size_t)c.max_batch_packets + 1)) != hipSuccess) return bad("seg staging");
     if (dmalloc(&x->d_seg_sess, sizeof(uint32_t) * (size_t)c.max_batch_packets) != hipSuccess) return bad("seg staging");
@@ -622,7 +641,7 @@ int edgpu_ctx_destroy(edgpu_ctx* x) {
     if (x->stream) (void)hipStreamSynchronize(x->stream);
     x->rings.release();                          // (every sender's rings)
     if (x->d_null) (void)hipFree(x->d_null);
-    x->d_sessions.release(); x->d_senders.release(); x->d_streams.release(); x->d_subs.release();
+    x->d_sessions.release(); x->d_senders.release(); x->d_streams.release(); x->d_stats.release(); x->d_subs.release();
     x->d_sub_index.release(); x->d_sub_range.release(); x->d_sub_pos.release(); x->d_fansub.release(); x->d_sub_out.release(); x->d_work.release();
     x->d_blk_bytes.release(); x->d_blk_count.release(); x->d_blk_maxb.release(); x->d_blk_maxc.release();
     x->d_img_plan.release();
@@ -1003,6 +1022,7 @@ int edgpu_session_add(edgpu_ctx* x, const char* sdp, uint32_t sdp_len, int udp_p
         std::chrono::system_clock::now().time_since_epoch()).count();
     sh.src.resize(sh.ntracks);
     for (auto& h : sh.src) { h.rr_ssrc = (uint32_t)::rand(); h.cname = source_cname(wall_ms / 1000); }
+    for (const TrackHost& t : tracks) sh.clock_rate.push_back(rtpmap_clock_rate(t.name));
     const uint32_t nsnd = 2 * sh.ntracks;
     if (!reuse) {
         HIP_CHECK(x->d_sessions.reserve(sid + 1, x->stream));
@@ -1078,6 +1098,25 @@ int edgpu_session_add(edgpu_ctx* x, const char* sdp, uint32_t sdp_len, int udp_p
     return EDGPU_OK;
 }
 
+
+// ---- Per-stream reception statistics (edgpu_stream_stats_*; edgpu_stats.hip) ----
+static StatsParams stats_params(const edgpu_ctx* x, int64_t now) {
+    StatsParams p;
+    p.senders = x->d_senders.ptr;
+    p.stats = x->d_stats.ptr;
+    p.nstreams = (uint32_t)std::min<size_t>(x->nstreams, x->d_stats.cap);
+    p.nsenders = x->nsenders;
+    p.now = now;
+    return p;
+}
+// Disables `sh`'s statistics and zeroes its rows (stream-ordered after the kernels that write them).
+static int stats_clear(edgpu_ctx* x, SessionHost& sh) {
+    HIP_CHECK(hipMemsetAsync(x->d_stats.ptr + sh.first_stream, 0, sh.ntracks * sizeof(StatDev), x->stream));
+    sh.stats = false;
+    x->n_stats--;
+    return EDGPU_OK;
+}
+
 // Deactivates subscriber `handle`'s sub-streams (host mirror + device flag, enqueued; the caller
 // synchronises) and returns its SubDev range to the free list.
 static int detach_subscriber(edgpu_ctx* x, uint32_t handle) {
@@ -1123,6 +1162,8 @@ int edgpu_session_remove(edgpu_ctx* x, uint32_t session, uint32_t flags) {
         HIP_CHECK(rb.add(old.data(), x->d_senders.ptr + sh.first_sender, nsnd * sizeof(SenderDev)));
         HIP_CHECK(rb.run());
     }
+    // from here the session ends: its statistics with it (a removal refused above leaves them on)
+    if (sh.stats) { int r = stats_clear(x, sh); if (r) return r; }
     for (uint32_t i = 0; i < nsnd; i++) {
         const uint32_t gs = sh.first_sender + i;
         x->work_cap_needed -= ((uint64_t)old[i].pk_mask + 1) / 16 + 1;
@@ -1623,6 +1664,11 @@ static int enqueue_ingest(edgpu_ctx* x, const edgpu_pkt_desc* dd, uint32_t n, co
     if (tcp && !deframed) HIP_CHECK(launch_deframe(*tcp, x->stream));
     HIP_CHECK(launch_ingest(p, nseg, x->stream));
     HIP_CHECK(hist_mark(x, 2, 1));
+    if (x->n_stats) {                   // per-stream statistics over what was just enqueued
+        HIP_CHECK(hist_mark(x, 4, 0));
+        HIP_CHECK(launch_stream_stats(stats_params(x, 0), x->stream));
+        HIP_CHECK(hist_mark(x, 4, 1));
+    }
     x->timed_ingest = true;
     x->kf_share = true;                 // (the interleaved path reads its report on aux)
     x->pend_seg = ds; x->pend_seg_sess = dss; x->pend_nseg = nseg; x->pending = true;
@@ -2307,8 +2353,112 @@ int edgpu_counters_get(edgpu_ctx* x, edgpu_counters* out) {
     return EDGPU_OK;
 }
 
+int edgpu_stream_stats_enable(edgpu_ctx* x, uint32_t session, int64_t now_ms) {
+    if (!x || !live_session(x, session)) return fail(EDGPU_BAD_ARGUMENT, "bad session");
+    DEVICE_ENTER(x);
+    SessionHost& sh = x->sessions[session];
+    // rows past the old capacity start zeroed (disabled), like every row of a fresh table
+    const size_t old_cap = x->d_stats.cap;
+    HIP_CHECK(x->d_stats.reserve(x->nstreams, x->stream));
+    if (x->d_stats.cap > old_cap)
+        HIP_CHECK(hipMemsetAsync(x->d_stats.ptr + old_cap, 0, (x->d_stats.cap - old_cap) * sizeof(StatDev), x->stream));
+    if (!x->hist[4][0][0])
+        for (auto& s : x->hist[4]) for (auto& e : s) HIP_CHECK(hipEventCreate(&e));
+    // statistics start at the next packet: the senders' heads now
+    std::vector<SenderDev> snd(2 * sh.ntracks);
+    {
+        Readback rb(x);
+        HIP_CHECK(rb.add(snd.data(), x->d_senders.ptr + sh.first_sender, snd.size() * sizeof(SenderDev)));
+        HIP_CHECK(rb.run());
+    }
+    std::vector<StatDev> rows(sh.ntracks);
+    for (uint32_t t = 0; t < sh.ntracks; t++) {
+        StatDev& S = rows[t];
+        memset(&S, 0, sizeof(S));
+        S.enabled = 1;
+        S.clock_rate = sh.clock_rate[t];
+        S.sender = sh.first_sender + 2 * t;
+        S.head = snd[2 * t].head;
+        S.rtcp_head = snd[2 * t + 1].head;
+        S.last_sample_ms = now_ms;              // fLastBitRateSample (ReflectorStream.cpp:141)
+    }
+    HIP_CHECK(hipMemcpyAsync(x->d_stats.ptr + sh.first_stream, rows.data(), rows.size() * sizeof(StatDev),
+                             hipMemcpyHostToDevice, x->stream));
+    HIP_CHECK(wsync(x, x->stream));             // `rows` is on the stack
+    if (!sh.stats) { sh.stats = true; x->n_stats++; }
+    return EDGPU_OK;
+}
+
+int edgpu_stream_stats_disable(edgpu_ctx* x, uint32_t session) {
+    if (!x || !live_session(x, session)) return fail(EDGPU_BAD_ARGUMENT, "bad session");
+    if (!x->sessions[session].stats) return EDGPU_OK;
+    DEVICE_ENTER(x);
+    return stats_clear(x, x->sessions[session]);
+}
+
+// The UpdateBitRate call of a ReflectPackets (ReflectorStream.cpp:1054), for every enabled stream
+int edgpu_stream_stats_sample(edgpu_ctx* x, int64_t now_ms) {
+    if (!x) return fail(EDGPU_BAD_ARGUMENT, "ctx is NULL");
+    if (!x->n_stats) return EDGPU_OK;
+    DEVICE_ENTER(x);
+    HIP_CHECK(launch_stream_bitrate(stats_params(x, now_ms), x->stream));
+    return EDGPU_OK;
+}
+
+static int stats_read(edgpu_ctx* x, uint32_t session, std::vector<StatDev>& rows) {
+    if (!x || !live_session(x, session)) return fail(EDGPU_BAD_ARGUMENT, "bad session");
+    const SessionHost& sh = x->sessions[session];
+    if (!sh.stats)
+        return fail(EDGPU_ERR, "stream statistics are not enabled for session " + std::to_string(session) +
+                               " (edgpu_stream_stats_enable)");
+    DEVICE_ENTER(x);
+    rows.resize(sh.ntracks);
+    Readback rb(x);
+    HIP_CHECK(rb.add(rows.data(), x->d_stats.ptr + sh.first_stream, rows.size() * sizeof(StatDev)));
+    HIP_CHECK(rb.run());
+    return EDGPU_OK;
+}
+
+int edgpu_stream_stats_get(edgpu_ctx* x, uint32_t session, edgpu_stream_stats* out, uint32_t cap, uint32_t* n_tracks) {
+    std::vector<StatDev> rows;
+    if (int r = stats_read(x, session, rows)) return r;
+    if (n_tracks) *n_tracks = (uint32_t)rows.size();
+    if (rows.size() > cap || !out) return fail(EDGPU_BAD_ARGUMENT, "more tracks than `cap`");
+    for (size_t t = 0; t < rows.size(); t++) {
+        const StatDev& S = rows[t];
+        edgpu_stream_stats& o = out[t];
+        memset(&o, 0, sizeof(o));
+        o.track = (uint32_t)t; o.clock_rate = S.clock_rate;
+        o.packets = S.packets; o.bytes = S.bytes; o.missed = S.missed; o.short_packets = S.short_packets;
+        o.has_src = S.has_src; o.ssrc = S.ssrc; o.ssrc_changes = S.ssrc_changes;
+        o.base_seq = S.base_seq; o.max_seq = S.max_seq; o.cycles = S.cycles; o.bad_seq = S.bad_seq;
+        o.received = S.received; o.misordered = S.misordered; o.restarts = S.restarts;
+        // RFC 3550 A.3: extended highest sequence number - base + 1
+        o.expected = S.has_src ? S.cycles + S.max_seq - S.base_seq + 1 : 0u;
+        o.lost = (int64_t)o.expected - (int64_t)S.received;
+        o.jitter = S.jitter >> 4; o.jitter_scaled = S.jitter;
+        o.has_transit = S.has_transit; o.transit = S.transit;
+        o.rtcp_packets = S.rtcp_packets; o.rtcp_bytes = S.rtcp_bytes; o.rtcp_missed = S.rtcp_missed;
+        o.sr_count = S.sr_count; o.sr_rtp = S.sr_rtp; o.sr_ntp = S.sr_ntp;
+        o.sr_packets = S.sr_packets; o.sr_octets = S.sr_octets; o.sr_arrival_ms = S.sr_arrival_ms;
+        o.interval_bytes = S.interval_bytes; o.bitrate = S.bitrate; o.last_sample_ms = S.last_sample_ms;
+    }
+    return EDGPU_OK;
+}
+
+// ReflectorSession::GetBitRate (ReflectorSession.cpp:297-309)
+int edgpu_session_bitrate(edgpu_ctx* x, uint32_t session, uint32_t* bps) {
+    if (!bps) return fail(EDGPU_BAD_ARGUMENT, "NULL argument");
+    std::vector<StatDev> rows;
+    if (int r = stats_read(x, session, rows)) return r;
+    uint32_t sum = 0;
+    for (const StatDev& S : rows) sum += S.bitrate;
+    *bps = sum;
+    return EDGPU_OK;
+}
+
 int edgpu_kernel_times(edgpu_ctx* x, int which, float* out_ms, uint32_t max_n, uint32_t* out_n) {
-    if (!x || which < 0 || which > 3 || (!out_ms && max_n)) return fail(EDGPU_BAD_ARGUMENT, "bad argument");
+    if (!x || which < 0 || which > 4 || (!out_ms && max_n)) return fail(EDGPU_BAD_ARGUMENT, "bad argument");
     DEVICE_ENTER(x);
     HIP_CHECK(sync_all(x));
     const uint32_t n = std::min<uint32_t>(x->hist_n[which] - x->hist_rd[which], edgpu_ctx::kHist);

@@ -214,6 +214,18 @@ struct BlockedParams {
     TickTotals* totals;
 };
 
+// Per-stream reception statistics (edgpu_stats.hip): k_stream_stats after every ingest while a
+// session is enabled, k_stream_bitrate at edgpu_stream_stats_sample.
+struct StatsParams {
+    const SenderDev* senders;
+    StatDev* stats;
+    uint32_t nstreams;          // rows of `stats`
+    uint32_t nsenders;          // rows of `senders` (a row naming a sender outside them is skipped)
+    int64_t now;                // k_stream_bitrate: the sample's clock
+};
+hipError_t launch_stream_stats(const StatsParams& p, hipStream_t st);
+hipError_t launch_stream_bitrate(const StatsParams& p, hipStream_t st);
+
 struct ImageParams {
     SenderDev* senders;
     SessionDev* sessions;

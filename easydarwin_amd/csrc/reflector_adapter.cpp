@@ -182,6 +182,7 @@ int Reflector::RemoveSession(uint32_t session, bool killOutputs) {
     // the engine first: if it refuses (outputs still attached without killOutputs, a device
     // error), the session lives on and its pushes keep flowing
     if ((err = edgpu_session_remove(fCtx, session, killOutputs ? EDGPU_SESSION_KILL_OUTPUTS : 0))) return err;
+    StatsOff(session);                                      // the engine cleared its statistics
     {
         // later pushes to it are dropped, and what another thread pushed since the flush is
         // discarded (its id may be reused by the next session)
@@ -463,6 +464,10 @@ int Reflector::ReflectPacketsLocked(int64_t nowMs, OutputSink* sink) {
     fTick.fanout_ms = fTick.readback_ms = fTick.write_ms = 0;
     fTick.passes = 0;
     fTick.stream_errors = 0;
+    // fStream->UpdateBitRate(currentTime) at the head of a ReflectPackets (ReflectorStream.cpp:1054)
+    // (through fSampleStats, not a direct call: the adapter also links against stand-in engines
+    // without the statistics entry points, reflector_stats.cpp)
+    if (fNumStats && (err = fSampleStats(fCtx, nowMs))) return err;
     edgpu_fanout_result res;
     if ((err = edgpu_fanout(fCtx, nowMs, &res))) return err;
     uint32_t nrr = 0;

@@ -176,6 +176,16 @@ public:
     // the sessions marked with a stream error (a sender ring lost a packet one of their outputs
     // needed) since the last call, and clears them: edgpu_stream_errors
     int StreamErrors(std::vector<uint32_t>* sessions);
+    // Per-stream reception statistics and the reference's bitrate (edgpu_stream_stats_*).  Enabling
+    // first ingests what was pushed so far, so the statistics start at the next pushed packet;
+    // while any session is enabled ReflectPackets(now) runs the bitrate sample step at `now`, as
+    // ReflectorSender::ReflectPackets calls UpdateBitRate (ReflectorStream.cpp:1054).
+    int  EnableStreamStats(uint32_t session, int64_t nowMs);
+    int  DisableStreamStats(uint32_t session);
+    // one record per track, over the packets ingested so far
+    int  GetStreamStats(uint32_t session, std::vector<edgpu_stream_stats>* out);
+    // ReflectorSession::GetBitRate (ReflectorSession.cpp:297-309); 0 while the session is not enabled
+    uint32_t GetBitRate(uint32_t session);
     // diagnostics: one wave on the engine stream waits `us` of the device clock (edgpu_debug_stall)
     int DebugStall(uint32_t us);
     // the message of the last ReflectPackets failure that happened on another thread than the
@@ -196,6 +206,12 @@ private:
     // thread's hold of fEngineMu, given up during writes when fConcurrent; fDelivering is true from
     // a tick's first write to its backpressure report (waiters: fIdleCv on fEngineMu)
     std::mutex fEngineMu;
+    std::vector<uint8_t> fStatsOn;                          // per session: EnableStreamStats (fEngineMu)
+    uint32_t fNumStats = 0;
+    int (*fSampleStats)(edgpu_ctx*, int64_t) = nullptr;     // edgpu_stream_stats_sample once enabled
+    void StatsOff(uint32_t session) {
+        if (session < fStatsOn.size() && fStatsOn[session]) { fStatsOn[session] = 0; fNumStats--; }
+    }
     std::condition_variable fIdleCv;
     bool fDelivering = false;
     bool fConcurrent = false;

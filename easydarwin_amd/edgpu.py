@@ -44,6 +44,8 @@ EXPORTED = [
     "edgpu_egress_block_info", "edgpu_session_remote_join", "edgpu_session_remote_leave",
     "edgpu_subscriber_set_slot", "edgpu_device_local_cpus", "edgpu_debug_stall",
     "edgpu_ipc_export", "edgpu_ipc_open", "edgpu_ipc_close", "edgpu_copy_to_device",
+    "edgpu_stream_stats_enable", "edgpu_stream_stats_disable", "edgpu_stream_stats_sample",
+    "edgpu_stream_stats_get", "edgpu_session_bitrate",
 ]
 IPC_HANDLE_BYTES = 64
 TCP_MESSAGE, TCP_DROPPED = 1, 2
@@ -154,7 +156,28 @@ class Counters(C.Structure):
                 ("kernel_launches", C.c_uint64), ("host_syncs", C.c_uint64)]
 
 
+class StreamStats(C.Structure):
+    """edgpu_stream_stats: one track's reception statistics (RFC 3550 A.1 / A.8) and the
+    reference's per-stream bitrate state."""
+    _fields_ = [("track", C.c_uint32), ("clock_rate", C.c_uint32),
+                ("packets", C.c_uint64), ("bytes", C.c_uint64), ("missed", C.c_uint64),
+                ("short_packets", C.c_uint32), ("has_src", C.c_uint32), ("ssrc", C.c_uint32),
+                ("ssrc_changes", C.c_uint32),
+                ("base_seq", C.c_uint32), ("max_seq", C.c_uint32), ("cycles", C.c_uint32), ("bad_seq", C.c_uint32),
+                ("received", C.c_uint32), ("misordered", C.c_uint32), ("restarts", C.c_uint32),
+                ("expected", C.c_uint32), ("lost", C.c_int64),
+                ("jitter", C.c_uint32), ("jitter_scaled", C.c_uint32),
+                ("has_transit", C.c_uint32), ("transit", C.c_uint32),
+                ("rtcp_packets", C.c_uint64), ("rtcp_bytes", C.c_uint64), ("rtcp_missed", C.c_uint64),
+                ("sr_count", C.c_uint32), ("sr_rtp", C.c_uint32), ("sr_ntp", C.c_uint64),
+                ("sr_packets", C.c_uint32), ("sr_octets", C.c_uint32), ("sr_arrival_ms", C.c_int64),
+                ("interval_bytes", C.c_uint32), ("bitrate", C.c_uint32), ("last_sample_ms", C.c_int64)]
+
+
 # numpy mirrors (same layout as the C structs)
+_NP_OF = {C.c_uint32: "<u4", C.c_uint64: "<u8", C.c_int64: "<i8"}
+STREAM_STATS_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in StreamStats._fields_])
+assert STREAM_STATS_DTYPE.itemsize == C.sizeof(StreamStats) == 176
 PKT_DTYPE = np.dtype([("slot", "<u4"), ("len", "<u2"), ("channel", "u1"), ("flags", "u1"),
                       ("arrival_ms", "<i8")])
 OUT_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u4"), ("packet_id", "<u4")])
@@ -270,6 +293,11 @@ def load(path: str = LIB_PATH):
         "edgpu_egress_clock": (I32, [P, C.c_int64]),
         "edgpu_egress_block_info": (I32, [P, P, U32, C.POINTER(U32)]),
         "edgpu_fanout_arrivals": (I32, [P, P, U32, I32]),
+        "edgpu_stream_stats_enable": (I32, [P, U32, I64]),
+        "edgpu_stream_stats_disable": (I32, [P, U32]),
+        "edgpu_stream_stats_sample": (I32, [P, I64]),
+        "edgpu_stream_stats_get": (I32, [P, U32, P, U32, C.POINTER(U32)]),
+        "edgpu_session_bitrate": (I32, [P, U32, C.POINTER(U32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -518,6 +546,31 @@ class Context:
     def sync(self):
         _check(self.lib.edgpu_sync(self.h))
 
+    def stream_stats_enable(self, session: int, now_ms: int):
+        """Zeroes and enables the session's per-stream statistics; they start at the next packet
+        (edgpu_stream_stats_enable)."""
+        _check(self.lib.edgpu_stream_stats_enable(self.h, session, int(now_ms)))
+
+    def stream_stats_disable(self, session: int):
+        _check(self.lib.edgpu_stream_stats_disable(self.h, session))
+
+    def stream_stats_sample(self, now_ms: int):
+        """The bitrate sample step (ReflectorStream::UpdateBitRate) at the tick's clock."""
+        _check(self.lib.edgpu_stream_stats_sample(self.h, int(now_ms)))
+
+    def stream_stats(self, session: int) -> np.ndarray:
+        """One STREAM_STATS_DTYPE record per track of `session` (edgpu_stream_stats_get)."""
+        out = np.zeros(16, dtype=STREAM_STATS_DTYPE)
+        n = C.c_uint32()
+        _check(self.lib.edgpu_stream_stats_get(self.h, session, _ptr(out), len(out), C.byref(n)))
+        return out[:n.value]
+
+    def session_bitrate(self, session: int) -> int:
+        """ReflectorSession::GetBitRate: the sum of the session's streams' bitrates (bits / s)."""
+        v = C.c_uint32()
+        _check(self.lib.edgpu_session_bitrate(self.h, session, C.byref(v)))
+        return v.value
+
     def debug_stall(self, us: int):
         """edgpu_debug_stall: one wave on the context stream waits `us` microseconds of the device
         clock -- work the GPU watchdog (watchdog_ms) can time out on."""
@@ -545,7 +598,7 @@ class Context:
         _check(self.lib.edgpu_set_timing(self.h, level))
 
     def kernel_times(self, which: int) -> list:
-        """which: 0 fan-out kernel, 1 whole fan-out tick, 2 ingest, 3 keyframe index."""
+        """which: 0 fan-out kernel, 1 whole fan-out tick, 2 ingest, 3 keyframe index, 4 stream statistics."""
         buf = (C.c_float * 256)()
         n = C.c_uint32()
         _check(self.lib.edgpu_kernel_times(self.h, which, buf, 256, C.byref(n)))

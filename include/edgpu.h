@@ -748,11 +748,96 @@ typedef struct edgpu_counters {
 } edgpu_counters;
 int  edgpu_counters_get(edgpu_ctx* ctx, edgpu_counters* out);
 
+/* ---- Per-stream reception statistics and the reference's per-stream bitrate ----
+ * Opt-in per push session.  While at least one session of the context is enabled, every ingest
+ * (edgpu_ingest of any pointer kind, edgpu_ingest_interleaved) is followed on the context stream
+ * by one read-only kernel that walks, per enabled track, the packets enqueued since its last
+ * launch; with no session enabled nothing is launched, recorded or copied.
+ *
+ * A "packet" is a queue entry with its final length: after the 2060-byte clamp (Q11), the SSRC
+ * filter's zeroing (FilterInvalidSSRCs) and the receive-time trailer strip.  Entries of length 0
+ * are skipped everywhere.
+ *
+ * RTP sender of a track: `packets` / `bytes` count every packet; one shorter than 12 bytes
+ * counts in `short_packets` and nothing else.  The others run, in queue order, RFC 3550 A.1
+ * update_seq without probation (MAX_DROPOUT 3000, MAX_MISORDER 100) on bytes 2-3 (seq), and the
+ * A.8 interarrival jitter on bytes 4-7 (timestamp) against the arrival time scaled to the
+ * track's clock rate: arrival_rtp = (u32)((u64)arrival_ms * clock_rate / 1000).  The first such
+ * packet, and one whose SSRC (bytes 8-11) differs from the current one (counted in
+ * `ssrc_changes`), restarts the sequence state, `received` and the jitter.  A jump of 3000 or
+ * more is not accepted until its successor arrives (`restarts`); a packet fewer than 100 behind
+ * is accepted and counted in `misordered`.  expected = cycles + max_seq - base_seq + 1 (mod 2^32;
+ * 0 before the first such packet), lost = expected - received.  clock_rate is the number after
+ * the first '/' of the track's rtpmap name (edgpu_sdp_track.name: "H264/90000" gives 90000,
+ * "MPEG4-GENERIC/44100/2" 44100); a name without one gives 0 and jitter stays 0.  `missed`
+ * counts packets that left a ring before they were examined (a single batch larger than the
+ * ring).
+ *
+ * RTCP sender: `rtcp_packets` / `rtcp_bytes` likewise; a packet of 28 bytes or more whose byte 1
+ * is 200 is a sender report: sr_ntp = bytes 8-15, sr_rtp 16-19, sr_packets 20-23, sr_octets
+ * 24-27, sr_arrival_ms its arrival; the last one wins.
+ *
+ * Bitrate: ReflectorStream::UpdateBitRate (APIModules/QTSSReflectorModule/ReflectorStream.h:
+ * 542-557), bit for bit.  interval_bytes += len (32-bit, wrapping) for every packet of every
+ * sender of the stream that is RTP by port parity (ReflectorStream.cpp:1947; on an
+ * RTSP-interleaved push both channels, Q12; on a UDP push the even port only).  The sample step
+ * at `now` runs when last_sample_ms + 30000 < now: bps = (float)(u32)(interval_bytes * 8) /
+ * (float)(now - last_sample_ms); bps *= 1000; bitrate = (u32)bps; interval_bytes = 0;
+ * last_sample_ms = now.
+ *
+ * Statistics belong to the owning context: they do not travel in session images, a replica
+ * session starts disabled, and edgpu_session_remove disables and clears them. */
+typedef struct edgpu_stream_stats {
+    uint32_t track;
+    uint32_t clock_rate;
+    /* RTP sender */
+    uint64_t packets, bytes;
+    uint64_t missed;
+    uint32_t short_packets;
+    uint32_t has_src, ssrc, ssrc_changes;
+    uint32_t base_seq, max_seq, cycles, bad_seq;
+    uint32_t received, misordered, restarts;
+    uint32_t expected;
+    int64_t  lost;
+    uint32_t jitter;            /* RTP timestamp units (the filter's state >> 4) */
+    uint32_t jitter_scaled;     /* the filter's state, scaled by 16 */
+    uint32_t has_transit, transit;
+    /* RTCP sender */
+    uint64_t rtcp_packets, rtcp_bytes, rtcp_missed;
+    uint32_t sr_count, sr_rtp;
+    uint64_t sr_ntp;
+    uint32_t sr_packets, sr_octets;
+    int64_t  sr_arrival_ms;
+    /* bitrate */
+    uint32_t interval_bytes, bitrate;
+    int64_t  last_sample_ms;
+} edgpu_stream_stats;
+/* Zeroes the statistics of `session`'s tracks and enables them.  last_sample_ms = now_ms, the
+ * fLastBitRateSample of the ReflectorStream constructor (ReflectorStream.cpp:141); statistics
+ * start at the next packet enqueued.  Enabling an enabled session resets it.  EDGPU_BAD_ARGUMENT
+ * for an unknown session.  Syncs. */
+int  edgpu_stream_stats_enable(edgpu_ctx* ctx, uint32_t session, int64_t now_ms);
+/* Disables and clears them (no-op for a session not enabled). */
+int  edgpu_stream_stats_disable(edgpu_ctx* ctx, uint32_t session);
+/* The UpdateBitRate call of a ReflectPackets (ReflectorStream.cpp:1054) for every enabled stream:
+ * a host calls it with the `now` it gives edgpu_fanout.  Does nothing while no session is
+ * enabled. */
+int  edgpu_stream_stats_sample(edgpu_ctx* ctx, int64_t now_ms);
+/* One record per track of `session`; *n_tracks receives the count (EDGPU_BAD_ARGUMENT if it
+ * exceeds `cap`).  EDGPU_ERR when the session is not enabled.  Syncs. */
+int  edgpu_stream_stats_get(edgpu_ctx* ctx, uint32_t session, edgpu_stream_stats* out, uint32_t cap,
+                            uint32_t* n_tracks);
+/* ReflectorSession::GetBitRate (ReflectorSession.cpp:297-309): the sum of the session's streams'
+ * bitrates -- what the reference puts into qtssCliSesMovieAverageBitRate at PLAY
+ * (QTSSReflectorModule.cpp:1951-1952) and into the stream-info record (ReflectorSession.cpp:372).
+ * EDGPU_ERR when the session is not enabled.  Syncs. */
+int  edgpu_session_bitrate(edgpu_ctx* ctx, uint32_t session, uint32_t* bps);
+
 /* Per-launch device durations (ms, HIP events on the ctx stream) recorded since the last
  * call, oldest first, for `which` = 0 fan-out copy kernel, 1 whole fan-out tick (plan +
  * copy), 2 ingest (with the keyframe index it carries), 3 keyframe index (no entries since the
- * index runs inside the ingest kernel).  Up to 256 launches are kept; the history is cleared
- * after reading.  Syncs. */
+ * index runs inside the ingest kernel), 4 the stream-statistics kernel (recorded only at
+ * EDGPU_TIMING_ALL).  Up to 256 launches are kept; the history is cleared after reading.  Syncs. */
 int  edgpu_kernel_times(edgpu_ctx* ctx, int which, float* out_ms, uint32_t max_n, uint32_t* out_n);
 
 /* Which per-launch timing events the context records from now on (default EDGPU_TIMING_ALL).
