@@ -182,8 +182,54 @@ struct StatDev {                    // 192 B
 };
 static_assert(sizeof(StatDev) == 192, "StatDev layout");
 
+// The H.264 elementary-stream tap (edgpu_tap_*, edgpu_tap.hip), indexed like StreamDev.  A row has
+// one writer at a time: the wave of k_tap_scan that owns the tap writes the drain's outcome (d_*),
+// k_tap_place's lane for the tap its placement (p_*) and, when the drain commits, the carried state.
+// All zero while disabled.
+struct TapDev {                     // 256 B
+    uint32_t enabled, sender;       // the track's RTP sender
+    uint32_t session, track;
+    uint64_t rec;                   // TapRec[cap]: one per queue entry of a drain
+    uint64_t unit;                  // edgpu_tap_unit[cap]: the drain's units, offsets relative to the stream
+    uint32_t cap, _pad0;            // the sender's meta-ring capacity when the buffers were sized
+    // carried between drains
+    uint64_t head;                  // next queue index to examine
+    uint32_t has_prev, prev_seq, pending, _pad1;
+    uint64_t packets, skipped, malformed, orphans, unsupported, missed, units, damaged_units;
+    // the drain being made
+    uint64_t d_start, d_cut;        // first intact index examined; the head if the drain commits
+    uint64_t d_bytes;
+    uint32_t d_nrec, d_nunits;      // records [0, d_cut - d_start) and units to deliver
+    uint32_t d_has_prev, d_prev_seq, d_pending, d_damaged;
+    uint32_t d_packets, d_skipped, d_malformed, d_orphans, d_unsupported, _pad2;
+    uint64_t p_offset;              // of the stream in `out`
+    uint32_t p_unit_first, _pad3;
+    uint64_t _pad4[5];
+};
+static_assert(sizeof(TapDev) == 256, "TapDev layout");
+
+// What one queue entry contributes to a drain's bytes (k_tap_scan -> k_tap_copy).
+enum : uint8_t { kTapNone = 0, kTapRaw = 1, kTapStart = 2, kTapStartHdr = 3, kTapStap = 4 };
+struct TapRec {                     // 16 B
+    uint64_t dst;                   // offset in the stream's bytes
+    uint16_t src;                   // offset in the slot of the first byte copied (kTapStap: of the first size field)
+    uint16_t len;                   // bytes copied after the prefix
+    uint8_t  kind;                  // prefix: none / 00 00 00 01 / 00 00 00 01 + hdr; kTapStap: `nunits` units
+    uint8_t  hdr;                   // rebuilt NAL header of an FU-A start
+    uint16_t nunits;
+};
+static_assert(sizeof(TapRec) == 16, "TapRec layout");
+
+struct TapPlace {                   // k_tap_place's verdict on a drain
+    uint64_t bytes;
+    uint32_t units, streams;
+    uint32_t commit;                // everything fits: k_tap_copy runs, the taps' state moved on
+    uint32_t n_items, n_uitems;     // k_tap_copy's work: rounds of records, rounds of units
+    uint32_t _pad;
+};
+
 struct SessionDev {
-    uint32_t first_sender;         // senders of track t: first_sender + 2t (+1 for RTCP)
+    uint32_t first_sender;        // senders of track t: first_sender + 2t (+1 for RTCP)
     uint32_t ntracks;
     uint32_t video_key_flag;        // ReflectorSession::fHasVideoKeyFrameUpdate
     uint32_t first_stream;

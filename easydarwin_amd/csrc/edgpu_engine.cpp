@@ -292,9 +292,10 @@ struct edgpu_ctx {
     static const int kHist = 256;
     // (ring 4, the stream-statistics kernel: its events are created by the first
     // edgpu_stream_stats_enable)
-    hipEvent_t hist[5][kHist][2] = {};
-    uint32_t hist_n[5] = {0, 0, 0, 0, 0};   // pairs recorded (monotonic sequence numbers)
-    uint32_t hist_rd[5] = {0, 0, 0, 0, 0};  // pairs already returned by edgpu_kernel_times
+    // (ring 5, a tap drain's kernels: by the first edgpu_tap_enable)
+    hipEvent_t hist[6][kHist][2] = {};
+    uint32_t hist_n[6] = {0, 0, 0, 0, 0, 0};   // pairs recorded (monotonic sequence numbers)
+    uint32_t hist_rd[6] = {0, 0, 0, 0, 0, 0};  // pairs already returned by edgpu_kernel_times
     // Borrowed end points.  A whole-tick entry (ring 1) ends at its copy kernel's end event
     // (ring 0 sequence number in tick_end[slot]); a keyframe entry (ring 3) starts at the end
     // event of the ingest it indexes (ring 2 sequence number in kf_from[slot]) when nothing ran
@@ -303,7 +304,7 @@ struct edgpu_ctx {
     static const uint32_t kOwnStart = 0xFFFFFFFFu;
     uint32_t tick_end[kHist] = {};
     uint32_t kf_from[kHist] = {};
-    uint32_t last_seq[5] = {0, 0, 0, 0, 0}; // each ring's newest complete pair (edgpu_last_timings)
+    uint32_t last_seq[6] = {0, 0, 0, 0, 0, 0}; // each ring's newest complete pair (edgpu_last_timings)
     bool kf_share = false;                  // the last ingest's end event may start the keyframe entry
     uint64_t fanout_launches = 0;
     int64_t last_now = 0;               // clock of the last edgpu_fanout (backpressure reports)
@@ -333,6 +334,18 @@ struct edgpu_ctx {
     DevVec<StreamDev> d_streams;
     DevVec<StatDev> d_stats;            // allocated by the first edgpu_stream_stats_enable; zero rows = disabled
     uint32_t n_stats = 0;               // sessions with statistics enabled
+    // H.264 elementary-stream taps (edgpu_tap_*): everything below is allocated by the first
+    // edgpu_tap_enable; zero rows = disabled
+    struct TapHost { void* rec = nullptr; void* unit = nullptr; uint64_t cap = 0; uint32_t sender = 0; };
+    DevVec<TapDev> d_taps;
+    std::map<uint32_t, TapHost> taps;   // enabled taps by stream index: their work buffers
+    std::vector<std::pair<uint32_t, uint64_t>> tap_grown;   // (sender, packets) of tapped rings grown since the last drain
+    bool tap_list_dirty = false;
+    DevVec<uint32_t> d_tap_list, d_tap_items;
+    DevVec<uint8_t> d_tap_out;          // a drain's bytes on their way to host memory
+    DevVec<edgpu_tap_unit> d_tap_units;
+    DevVec<edgpu_tap_stream> d_tap_streams;
+    TapPlace* d_tap_place = nullptr;
     DevVec<SubDev> d_subs;
     DevVec<uint32_t> d_sub_index;
     DevVec<uint32_t> d_sub_range;
@@ -645,6 +658,10 @@ int edgpu_ctx_destroy(edgpu_ctx* x) {
     x->d_sub_index.release(); x->d_sub_range.release(); x->d_sub_pos.release(); x->d_fansub.release(); x->d_sub_out.release(); x->d_work.release();
     x->d_blk_bytes.release(); x->d_blk_count.release(); x->d_blk_maxb.release(); x->d_blk_maxc.release();
     x->d_img_plan.release();
+    for (auto& t : x->taps) { (void)hipFree(t.second.rec); (void)hipFree(t.second.unit); }
+    x->d_taps.release(); x->d_tap_list.release(); x->d_tap_items.release(); x->d_tap_out.release();
+    x->d_tap_units.release(); x->d_tap_streams.release();
+    if (x->d_tap_place) (void)hipFree(x->d_tap_place);
     x->d_carry.release(); x->d_tcp_groups.release(); x->d_tcp_reads.release(); x->d_tcp_chunk_group.release();
     x->d_tcp_ncand.release(); x->d_tcp_cands.release(); x->d_tcp_links.release(); x->d_tcp_chunkres.release();
     x->d_tcp_results.release(); x->d_tcp_offs.release(); x->d_tcp_stage.release(); x->d_blocked.release();
@@ -812,6 +829,7 @@ static int grow_sender(edgpu_ctx* x, uint32_t sender, uint64_t want_pk, uint64_t
     x->work_cap_needed += new_pk / 16 - old_pk / 16;
     x->ring_bytes += (new_pk - old_pk) * (sizeof(PktMeta) + sizeof(uint32_t)) + (new_by - old_by);
     x->ring_grows++;
+    if (new_pk > old_pk && !x->taps.empty()) x->tap_grown.emplace_back(sender, new_pk);   // (its tap's work buffers follow)
     x->index_dirty = true;                      // the work list is sized from the rings
     *grown = true;
     return EDGPU_OK;
@@ -1117,6 +1135,20 @@ static int stats_clear(edgpu_ctx* x, SessionHost& sh) {
     return EDGPU_OK;
 }
 
+// Disables the tap of stream row `row` (if any): its row zeroed, its work buffers freed.  The
+// kernels that use them have finished (every drain syncs).
+static int tap_clear(edgpu_ctx* x, uint32_t row) {
+    auto it = x->taps.find(row);
+    if (it == x->taps.end()) return EDGPU_OK;
+    HIP_CHECK(hipMemsetAsync(x->d_taps.ptr + row, 0, sizeof(TapDev), x->stream));
+    HIP_CHECK(wsync(x, x->stream));
+    (void)hipFree(it->second.rec);
+    (void)hipFree(it->second.unit);
+    x->taps.erase(it);
+    x->tap_list_dirty = true;
+    return EDGPU_OK;
+}
+
 // Deactivates subscriber `handle`'s sub-streams (host mirror + device flag, enqueued; the caller
 // synchronises) and returns its SubDev range to the free list.
 static int detach_subscriber(edgpu_ctx* x, uint32_t handle) {
@@ -1164,6 +1196,7 @@ int edgpu_session_remove(edgpu_ctx* x, uint32_t session, uint32_t flags) {
     }
     // from here the session ends: its statistics with it (a removal refused above leaves them on)
     if (sh.stats) { int r = stats_clear(x, sh); if (r) return r; }
+    for (uint32_t t = 0; t < sh.ntracks; t++) { int r = tap_clear(x, sh.first_stream + t); if (r) return r; }
     for (uint32_t i = 0; i < nsnd; i++) {
         const uint32_t gs = sh.first_sender + i;
         x->work_cap_needed -= ((uint64_t)old[i].pk_mask + 1) / 16 + 1;
@@ -2457,8 +2490,135 @@ int edgpu_session_bitrate(edgpu_ctx* x, uint32_t session, uint32_t* bps) {
     return EDGPU_OK;
 }
 
+// ---- H.264 elementary-stream taps (edgpu_tap_*; edgpu_tap.hip) ----
+static int tap_buffers(edgpu_ctx* x, edgpu_ctx::TapHost& h, uint64_t cap) {
+    void* rec = nullptr; void* unit = nullptr;
+    if (dmalloc(&rec, cap * sizeof(TapRec)) != hipSuccess) { (void)hipGetLastError(); return fail(EDGPU_OUT_OF_MEMORY, "tap records"); }
+    if (dmalloc(&unit, cap * sizeof(edgpu_tap_unit)) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipFree(rec);
+        return fail(EDGPU_OUT_OF_MEMORY, "tap units");
+    }
+    if (h.rec) (void)hipFree(h.rec);
+    if (h.unit) (void)hipFree(h.unit);
+    h.rec = rec; h.unit = unit; h.cap = cap;
+    return EDGPU_OK;
+}
+
+int edgpu_tap_enable(edgpu_ctx* x, uint32_t session, uint32_t track) {
+    if (!x || !live_session(x, session) || track >= x->sessions[session].ntracks) return fail(EDGPU_BAD_ARGUMENT, "bad session or track");
+    DEVICE_ENTER(x);
+    const SessionHost& sh = x->sessions[session];
+    const uint32_t row = sh.first_stream + track, sender = sh.first_sender + 2 * track;
+    SenderDev D;
+    {
+        Readback rb(x);
+        HIP_CHECK(rb.add(&D, x->d_senders.ptr + sender, sizeof(D)));
+        HIP_CHECK(rb.run());
+    }
+    if (!(D.flags & kSndH264))
+        return fail(EDGPU_BAD_ARGUMENT, "the tap depacketises H.264 only: the track's payload name is not \"H264/90000\"");
+    const size_t old_cap = x->d_taps.cap;
+    HIP_CHECK(x->d_taps.reserve(x->nstreams, x->stream));
+    if (x->d_taps.cap > old_cap)
+        HIP_CHECK(hipMemsetAsync(x->d_taps.ptr + old_cap, 0, (x->d_taps.cap - old_cap) * sizeof(TapDev), x->stream));
+    if (!x->d_tap_place && dmalloc(&x->d_tap_place, sizeof(TapPlace)) != hipSuccess) return fail(EDGPU_OUT_OF_MEMORY, "tap placement");
+    if (!x->hist[5][0][0])
+        for (auto& s : x->hist[5]) for (auto& e : s) HIP_CHECK(hipEventCreate(&e));
+    edgpu_ctx::TapHost& h = x->taps[row];
+    const uint64_t cap = (uint64_t)D.pk_mask + 1;
+    if (h.cap != cap) {
+        if (int r = tap_buffers(x, h, cap)) { if (!h.rec) x->taps.erase(row); return r; }
+    }
+    h.sender = sender;
+    TapDev T;
+    memset(&T, 0, sizeof(T));
+    T.enabled = 1; T.sender = sender; T.session = session; T.track = track;
+    T.rec = (uint64_t)(uintptr_t)h.rec; T.unit = (uint64_t)(uintptr_t)h.unit; T.cap = (uint32_t)cap;
+    T.head = D.head;                            // the tap starts at the next packet enqueued
+    HIP_CHECK(hipMemcpyAsync(x->d_taps.ptr + row, &T, sizeof(T), hipMemcpyHostToDevice, x->stream));
+    HIP_CHECK(wsync(x, x->stream));             // `T` is on the stack
+    x->tap_list_dirty = true;
+    return EDGPU_OK;
+}
+
+int edgpu_tap_disable(edgpu_ctx* x, uint32_t session, uint32_t track) {
+    if (!x || !live_session(x, session) || track >= x->sessions[session].ntracks) return fail(EDGPU_BAD_ARGUMENT, "bad session or track");
+    DEVICE_ENTER(x);
+    return tap_clear(x, x->sessions[session].first_stream + track);
+}
+
+int edgpu_tap_drain(edgpu_ctx* x, uint32_t flags, void* out, uint64_t out_cap, int ptr_kind, edgpu_tap_unit* units,
+                    uint32_t unit_cap, edgpu_tap_stream* streams, uint32_t stream_cap, edgpu_tap_result* result) {
+    if (!x || !result || (flags & ~EDGPU_TAP_FLUSH) || (!out && out_cap) || (!units && unit_cap) || (!streams && stream_cap))
+        return fail(EDGPU_BAD_ARGUMENT, "bad argument");
+    if (ptr_kind != EDGPU_PTR_HOST && ptr_kind != EDGPU_PTR_DEVICE && ptr_kind != EDGPU_PTR_PINNED)
+        return fail(EDGPU_BAD_ARGUMENT, "bad ptr_kind");
+    const bool device_out = ptr_kind == EDGPU_PTR_DEVICE;
+    if (device_out && ((uintptr_t)out & 15)) return fail(EDGPU_BAD_ARGUMENT, "a device `out` must be 16-B aligned");
+    memset(result, 0, sizeof(*result));
+    if (x->taps.empty()) return EDGPU_OK;       // nothing launched, allocated, recorded or copied
+    DEVICE_ENTER(x);
+    const uint32_t ntaps = (uint32_t)x->taps.size();
+    // tapped rings that grew: work buffers of the new capacity (no drain is in flight: every drain syncs)
+    for (const auto& g : x->tap_grown)
+        for (auto& t : x->taps)
+            if (t.second.sender == g.first && t.second.cap < g.second) {
+                if (int r = tap_buffers(x, t.second, g.second)) return r;
+                const uint64_t v[3] = {(uint64_t)(uintptr_t)t.second.rec, (uint64_t)(uintptr_t)t.second.unit, g.second};
+                HIP_CHECK(hipMemcpyAsync(&x->d_taps.ptr[t.first].rec, v, sizeof(v), hipMemcpyHostToDevice, x->stream));
+                HIP_CHECK(wsync(x, x->stream));
+            }
+    x->tap_grown.clear();
+    if (x->tap_list_dirty) {
+        std::vector<uint32_t> list;
+        for (const auto& t : x->taps) list.push_back(t.first);     // ascending rows: (session, track) order
+        HIP_CHECK(x->d_tap_list.reserve(ntaps, x->stream));
+        HIP_CHECK(x->d_tap_items.reserve(2 * ((size_t)ntaps + 1), x->stream));
+        HIP_CHECK(x->d_tap_streams.reserve(ntaps, x->stream));
+        HIP_CHECK(hipMemcpyAsync(x->d_tap_list.ptr, list.data(), ntaps * sizeof(uint32_t), hipMemcpyHostToDevice, x->stream));
+        HIP_CHECK(wsync(x, x->stream));         // `list` is on the stack
+        x->tap_list_dirty = false;
+    }
+    TapPlace pl;
+    for (int attempt = 0;; attempt++) {
+        TapParams p;
+        p.senders = x->d_senders.ptr; p.taps = x->d_taps.ptr; p.list = x->d_tap_list.ptr;
+        p.ntaps = ntaps; p.nsenders = x->nsenders; p.flags = flags;
+        p.unit_cap = (uint32_t)std::min<uint64_t>(unit_cap, x->d_tap_units.cap);
+        p.stream_cap = stream_cap;
+        p.out_cap = device_out ? out_cap : std::min<uint64_t>(out_cap, x->d_tap_out.cap);
+        p.out = device_out ? (uint8_t*)out : x->d_tap_out.ptr;
+        p.units = x->d_tap_units.ptr; p.streams = x->d_tap_streams.ptr;
+        p.items = x->d_tap_items.ptr; p.place = x->d_tap_place;
+        HIP_CHECK(hist_mark(x, 5, 0));
+        HIP_CHECK(launch_tap_drain(p, (uint32_t)std::max(x->num_cus * 4, 1), x->stream));
+        HIP_CHECK(hist_mark(x, 5, 1));
+        {
+            Readback rb(x);
+            HIP_CHECK(rb.add(&pl, x->d_tap_place, sizeof(pl)));
+            HIP_CHECK(rb.run());
+        }
+        if (pl.commit) break;
+        result->bytes = pl.bytes; result->units = pl.units; result->streams = pl.streams;
+        const bool fits = pl.bytes <= out_cap && pl.units <= unit_cap && pl.streams <= stream_cap;
+        if (!fits || attempt)
+            return fail(EDGPU_OUT_OVERFLOW, "tap drain: " + std::to_string(pl.bytes) + " bytes, " + std::to_string(pl.units) +
+                                            " units, " + std::to_string(pl.streams) + " streams needed; nothing was consumed");
+        // the caller has room, the context's staging did not: grown, and the drain made again
+        if (!device_out) HIP_CHECK(x->d_tap_out.reserve(pl.bytes, x->stream));
+        HIP_CHECK(x->d_tap_units.reserve(pl.units, x->stream));
+    }
+    result->bytes = pl.bytes; result->units = pl.units; result->streams = pl.streams;
+    Readback rb(x);
+    if (!device_out) HIP_CHECK(rb.add(out, x->d_tap_out.ptr, pl.bytes));
+    HIP_CHECK(rb.add(units, x->d_tap_units.ptr, (size_t)pl.units * sizeof(edgpu_tap_unit)));
+    HIP_CHECK(rb.add(streams, x->d_tap_streams.ptr, (size_t)pl.streams * sizeof(edgpu_tap_stream)));
+    HIP_CHECK(rb.run());
+    return EDGPU_OK;
+}
+
 int edgpu_kernel_times(edgpu_ctx* x, int which, float* out_ms, uint32_t max_n, uint32_t* out_n) {
-    if (!x || which < 0 || which > 4 || (!out_ms && max_n)) return fail(EDGPU_BAD_ARGUMENT, "bad argument");
+    if (!x || which < 0 || which > 5 || (!out_ms && max_n)) return fail(EDGPU_BAD_ARGUMENT, "bad argument");
     DEVICE_ENTER(x);
     HIP_CHECK(sync_all(x));
     const uint32_t n = std::min<uint32_t>(x->hist_n[which] - x->hist_rd[which], edgpu_ctx::kHist);

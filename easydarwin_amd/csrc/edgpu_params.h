@@ -226,6 +226,26 @@ struct StatsParams {
 hipError_t launch_stream_stats(const StatsParams& p, hipStream_t st);
 hipError_t launch_stream_bitrate(const StatsParams& p, hipStream_t st);
 
+// The H.264 elementary-stream tap (edgpu_tap.hip): one drain is k_tap_scan (a wave per enabled
+// tap), k_tap_place (one workgroup) and k_tap_copy.
+constexpr uint32_t kTapRound = EDGPU_TAP_ROUND;     // queue entries per scan round and per copy item
+struct TapParams {
+    const SenderDev* senders;
+    TapDev* taps;
+    const uint32_t* list;       // the enabled taps' rows, ascending
+    uint32_t ntaps;
+    uint32_t nsenders;
+    uint32_t flags;             // EDGPU_TAP_FLUSH
+    uint32_t unit_cap, stream_cap;
+    uint64_t out_cap;
+    uint8_t* out;
+    edgpu_tap_unit* units;      // device staging of the caller's arrays
+    edgpu_tap_stream* streams;
+    uint32_t* items;            // 2 x (ntaps + 1): exclusive sums of the taps' record rounds, unit rounds
+    TapPlace* place;
+};
+hipError_t launch_tap_drain(const TapParams& p, uint32_t copy_blocks, hipStream_t st);
+
 struct ImageParams {
     SenderDev* senders;
     SessionDev* sessions;

@@ -52,6 +52,7 @@
 #include <chrono>
 #include <memory>
 #include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <string>
@@ -186,6 +187,14 @@ public:
     int  GetStreamStats(uint32_t session, std::vector<edgpu_stream_stats>* out);
     // ReflectorSession::GetBitRate (ReflectorSession.cpp:297-309); 0 while the session is not enabled
     uint32_t GetBitRate(uint32_t session);
+    // The H.264 elementary-stream tap (edgpu_tap_*, reflector_tap.cpp).  Enabling first ingests what
+    // was pushed so far, so the tap starts at the next pushed packet.  DrainElementaryStreams ingests
+    // what is pending, drains every enabled tap (`flush`: the trailing incomplete unit too) and calls
+    // `sink` once per stream with its row, its units (offsets relative to `bytes`) and its bytes.
+    typedef std::function<void(const edgpu_tap_stream& stream, const edgpu_tap_unit* units, const uint8_t* bytes)> TapSink;
+    int  EnableElementaryStream(uint32_t session, uint32_t track);
+    int  DisableElementaryStream(uint32_t session, uint32_t track);
+    int  DrainElementaryStreams(const TapSink& sink, bool flush = false);
     // diagnostics: one wave on the engine stream waits `us` of the device clock (edgpu_debug_stall)
     int DebugStall(uint32_t us);
     // the message of the last ReflectPackets failure that happened on another thread than the

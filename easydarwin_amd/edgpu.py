@@ -46,6 +46,7 @@ EXPORTED = [
     "edgpu_ipc_export", "edgpu_ipc_open", "edgpu_ipc_close", "edgpu_copy_to_device",
     "edgpu_stream_stats_enable", "edgpu_stream_stats_disable", "edgpu_stream_stats_sample",
     "edgpu_stream_stats_get", "edgpu_session_bitrate",
+    "edgpu_tap_enable", "edgpu_tap_disable", "edgpu_tap_drain",
 ]
 IPC_HANDLE_BYTES = 64
 TCP_MESSAGE, TCP_DROPPED = 1, 2
@@ -174,10 +175,36 @@ class StreamStats(C.Structure):
                 ("interval_bytes", C.c_uint32), ("bitrate", C.c_uint32), ("last_sample_ms", C.c_int64)]
 
 
+class TapUnit(C.Structure):
+    """edgpu_tap_unit: one access unit of a tap drain."""
+    _fields_ = [("offset", C.c_uint64), ("bytes", C.c_uint32), ("rtp_ts", C.c_uint32), ("arrival_ms", C.c_int64),
+                ("flags", C.c_uint32), ("first_seq", C.c_uint32), ("n_packets", C.c_uint32), ("n_nals", C.c_uint32),
+                ("stream", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class TapStream(C.Structure):
+    """edgpu_tap_stream: one enabled tap's part of a drain and its cumulative counters."""
+    _fields_ = [("session", C.c_uint32), ("track", C.c_uint32), ("offset", C.c_uint64), ("bytes", C.c_uint64),
+                ("unit_first", C.c_uint32), ("unit_count", C.c_uint32),
+                ("packets", C.c_uint64), ("skipped", C.c_uint64), ("malformed", C.c_uint64), ("orphans", C.c_uint64),
+                ("unsupported", C.c_uint64), ("missed", C.c_uint64), ("units", C.c_uint64), ("damaged_units", C.c_uint64)]
+
+
+class TapResult(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("units", C.c_uint32), ("streams", C.c_uint32)]
+
+
+TAP_KEY, TAP_PARAMS, TAP_DAMAGED, TAP_NOMARKER, TAP_OPEN_END = 1, 2, 4, 8, 16
+TAP_FLUSH = 1
+TAP_ROUND = 64              # EDGPU_TAP_ROUND: queue entries per round of the scan kernel
+
 # numpy mirrors (same layout as the C structs)
 _NP_OF = {C.c_uint32: "<u4", C.c_uint64: "<u8", C.c_int64: "<i8"}
 STREAM_STATS_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in StreamStats._fields_])
 assert STREAM_STATS_DTYPE.itemsize == C.sizeof(StreamStats) == 176
+TAP_UNIT_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in TapUnit._fields_])
+TAP_STREAM_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in TapStream._fields_])
+assert TAP_UNIT_DTYPE.itemsize == C.sizeof(TapUnit) == 48 and TAP_STREAM_DTYPE.itemsize == C.sizeof(TapStream) == 96
 PKT_DTYPE = np.dtype([("slot", "<u4"), ("len", "<u2"), ("channel", "u1"), ("flags", "u1"),
                       ("arrival_ms", "<i8")])
 OUT_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u4"), ("packet_id", "<u4")])
@@ -298,6 +325,9 @@ def load(path: str = LIB_PATH):
         "edgpu_stream_stats_sample": (I32, [P, I64]),
         "edgpu_stream_stats_get": (I32, [P, U32, P, U32, C.POINTER(U32)]),
         "edgpu_session_bitrate": (I32, [P, U32, C.POINTER(U32)]),
+        "edgpu_tap_enable": (I32, [P, U32, U32]),
+        "edgpu_tap_disable": (I32, [P, U32, U32]),
+        "edgpu_tap_drain": (I32, [P, U32, P, U64, I32, P, U32, P, U32, C.POINTER(TapResult)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -570,6 +600,45 @@ class Context:
         v = C.c_uint32()
         _check(self.lib.edgpu_session_bitrate(self.h, session, C.byref(v)))
         return v.value
+
+    def tap_enable(self, session: int, track: int):
+        """Enables (or resets) the H.264 elementary-stream tap of a track, from the next packet
+        enqueued (edgpu_tap_enable)."""
+        _check(self.lib.edgpu_tap_enable(self.h, session, track))
+
+    def tap_disable(self, session: int, track: int):
+        _check(self.lib.edgpu_tap_disable(self.h, session, track))
+
+    def tap_drain_raw(self, flags, out_ptr, out_cap, ptr_kind, units: np.ndarray, streams: np.ndarray) -> tuple:
+        """edgpu_tap_drain as it is: (status, TapResult)."""
+        res = TapResult()
+        rc = self.lib.edgpu_tap_drain(self.h, flags, C.c_void_p(out_ptr), out_cap, ptr_kind,
+                                      _ptr(units) if len(units) else None, len(units),
+                                      _ptr(streams) if len(streams) else None, len(streams), C.byref(res))
+        return rc, res
+
+    def tap_drain(self, flush: bool = False, out=None):
+        """Drains every enabled tap (edgpu_tap_drain): (bytes, units, streams) -- a uint8 array (or
+        the byte count when `out` is a DeviceBuffer the kernel wrote), TAP_UNIT_DTYPE rows and
+        TAP_STREAM_DTYPE rows.  Grows its buffers and retries once on overflow (nothing is consumed
+        by a call that overflows); a device `out` is not grown."""
+        caps = getattr(self, "_tap_caps", [1 << 20, 4096, 64])
+        for attempt in range(2):
+            units = np.zeros(caps[1], dtype=TAP_UNIT_DTYPE)
+            streams = np.zeros(caps[2], dtype=TAP_STREAM_DTYPE)
+            if out is None:
+                buf = np.empty(caps[0], dtype=np.uint8)
+                rc, res = self.tap_drain_raw(TAP_FLUSH if flush else 0, buf.ctypes.data, buf.nbytes, PTR_HOST, units, streams)
+            else:
+                buf = None
+                rc, res = self.tap_drain_raw(TAP_FLUSH if flush else 0, out.ptr, out.nbytes, PTR_DEVICE, units, streams)
+            if rc != OUT_OVERFLOW or attempt:
+                break
+            caps = [max(caps[0], int(res.bytes)), max(caps[1], int(res.units)), max(caps[2], int(res.streams))]
+            self._tap_caps = caps
+        _check(rc)
+        data = buf[:res.bytes] if buf is not None else int(res.bytes)
+        return data, units[:res.units], streams[:res.streams]
 
     def debug_stall(self, us: int):
         """edgpu_debug_stall: one wave on the context stream waits `us` microseconds of the device

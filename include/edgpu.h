@@ -833,11 +833,104 @@ int  edgpu_stream_stats_get(edgpu_ctx* ctx, uint32_t session, edgpu_stream_stats
  * EDGPU_ERR when the session is not enabled.  Syncs. */
 int  edgpu_session_bitrate(edgpu_ctx* ctx, uint32_t session, uint32_t* bps);
 
+/* ---- H.264 elementary-stream tap ----
+ *
+ * An opt-in tap per H.264 track turns the track's RTP sender ring into an Annex-B elementary
+ * stream on the GPU (RFC 6184, non-interleaved mode: single NAL unit packets, STAP-A, FU-A), in
+ * whole access units with an index -- what a recorder, a segmenter or a snapshot service needs,
+ * without pulling RTP packets to the host.  With no tap enabled nothing is launched, allocated,
+ * recorded or copied; a tap reads the rings and never pins a packet: packets that leave a ring
+ * before a drain examined them are counted in `missed`.  tests/tap_model.py is the executable
+ * statement of the rules below.
+ *
+ * A drain takes the queue entries of the track's RTP sender in queue order from the tap's head,
+ * each with its final length (as the statistics see it); empty entries are ignored.
+ *   Parse.  A packet is bad if it is shorter than 12 bytes or its version is not 2.  The header is
+ *     12 + 4 CC bytes; with X the 4-byte extension header must fit and the header grows by 4 + 4 x
+ *     its BE16 length; with P the last byte is the pad count, bad if 0 or reaching into the header.
+ *     An empty payload is bad.  Bad packets count in `skipped` and are otherwise absent: their
+ *     sequence number is not trusted (a gap follows naturally if they had one).
+ *   Gap.  A good packet has a gap when a previous good packet exists and its sequence number is
+ *     not that packet's + 1 (mod 2^16).  Nothing is reordered.
+ *   Access units.  A good packet starts a unit if it is the first of a drain, its timestamp
+ *     differs from the previous good packet's, or that packet had the marker bit.
+ *   NALs, by payload[0] & 0x1F:  1..23: 00 00 00 01 + payload.  24 (STAP-A): after the first byte,
+ *     units of [BE16 size][NAL], each emitted as 00 00 00 01 + NAL; a size of 0 or one past the
+ *     payload ends the packet there (`malformed`).  28 (FU-A): with S and not E: 00 00 00 01, the
+ *     rebuilt header (payload[0] & 0xE0) | (payload[1] & 0x1F), payload[2..]; this opens a chain of
+ *     that type.  Without S: payload[2..] iff a chain of the same type is open, the packet has no
+ *     gap and starts no unit (E closes the chain); otherwise it is dropped (`orphans`) and the
+ *     chain closes.  S and E together, or a payload of one byte: dropped (`malformed`), the chain
+ *     closes.  Every other packet closes the chain.  0, 25..27, 29..31: dropped (`unsupported`).
+ *   Flags.  KEY: an emitted NAL of type 5.  PARAMS: one of type 7 or 8.  NOMARKER: the unit's last
+ *     packet has no marker.  OPEN_END: emitted by a flush.  DAMAGED: a packet of the unit has a gap
+ *     (the previous unit too when its last packet had no marker), a packet of it was dropped, a
+ *     chain is open at its last packet, or packets were missed before it.
+ *   Whole units only.  A unit is complete when its last packet has the marker or a later good
+ *     packet is enqueued.  A drain consumes the complete units: the head moves just past the last
+ *     packet of the last one, the rest waits.  EDGPU_TAP_FLUSH emits the trailing unit too and
+ *     consumes everything.  The counters count consumed entries.
+ * Between drains a tap carries its head, the previous good packet's sequence number, a
+ * pending-damage bit and the counters.  Taps belong to the owning context: they do not travel in
+ * session images, a replica session starts without them, edgpu_session_remove clears them.
+ * Out of scope: MP4 / TS muxing, audio, packetization-mode 2, H.265, reordering. */
+#define EDGPU_TAP_KEY       1u
+#define EDGPU_TAP_PARAMS    2u
+#define EDGPU_TAP_DAMAGED   4u
+#define EDGPU_TAP_NOMARKER  8u
+#define EDGPU_TAP_OPEN_END 16u
+#define EDGPU_TAP_FLUSH     1u      /* edgpu_tap_drain flags */
+#define EDGPU_TAP_ROUND    64u      /* queue entries the scan kernel examines per round */
+typedef struct edgpu_tap_unit {     /* one access unit */
+    uint64_t offset;            /* of its first byte in `out` */
+    uint32_t bytes;             /* 0: the unit emitted nothing (it still reports DAMAGED) */
+    uint32_t rtp_ts;
+    int64_t  arrival_ms;        /* of its first packet */
+    uint32_t flags;             /* EDGPU_TAP_KEY ... */
+    uint32_t first_seq;
+    uint32_t n_packets;         /* good packets, emitted or dropped */
+    uint32_t n_nals;            /* start codes emitted */
+    uint32_t stream;            /* index of its edgpu_tap_stream row */
+    uint32_t _pad;
+} edgpu_tap_unit;
+typedef struct edgpu_tap_stream {   /* one enabled tap, in (session, track) order */
+    uint32_t session, track;
+    uint64_t offset;            /* 16-B aligned; the stream's units follow each other from here */
+    uint64_t bytes;
+    uint32_t unit_first, unit_count;
+    /* cumulative since the tap was enabled */
+    uint64_t packets;           /* non-empty entries consumed */
+    uint64_t skipped, malformed, orphans, unsupported, missed;
+    uint64_t units, damaged_units;
+} edgpu_tap_stream;
+typedef struct edgpu_tap_result {
+    uint64_t bytes;             /* of `out` used (or needed) */
+    uint32_t units, streams;    /* rows written (or needed) */
+} edgpu_tap_result;
+/* Enables (or resets) the tap of `track`, from the next packet enqueued.  EDGPU_BAD_ARGUMENT
+ * unless the track's payload name is exactly "H264/90000".  The first enable allocates the
+ * context's tap tables; each tap holds work buffers sized from its sender's ring.  Syncs. */
+int  edgpu_tap_enable(edgpu_ctx* ctx, uint32_t session, uint32_t track);
+/* Disables and clears it (no-op for a tap not enabled).  Syncs. */
+int  edgpu_tap_disable(edgpu_ctx* ctx, uint32_t session, uint32_t track);
+/* Drains every enabled tap in one call, on the context stream (after every earlier ingest), and
+ * syncs.  `out` receives the bytes: device memory the kernel writes directly (EDGPU_PTR_DEVICE, 16-B
+ * aligned) or host memory (EDGPU_PTR_HOST / EDGPU_PTR_PINNED: the kernel writes a context-owned
+ * device buffer that grows on demand, read back before the call returns).  `units` and `streams`
+ * are host arrays.  If the bytes, the units or the stream rows do not fit, the call returns
+ * EDGPU_OUT_OVERFLOW, `result` holds the sizes needed and nothing is consumed: no head, counter
+ * or state changes, and a retry with room yields what a first call would have.  No byte of `out`
+ * outside [offset, roundup16(offset + bytes)) of some stream is written. */
+int  edgpu_tap_drain(edgpu_ctx* ctx, uint32_t flags, void* out, uint64_t out_cap, int ptr_kind,
+                     edgpu_tap_unit* units, uint32_t unit_cap, edgpu_tap_stream* streams, uint32_t stream_cap,
+                     edgpu_tap_result* result);
+
 /* Per-launch device durations (ms, HIP events on the ctx stream) recorded since the last
  * call, oldest first, for `which` = 0 fan-out copy kernel, 1 whole fan-out tick (plan +
  * copy), 2 ingest (with the keyframe index it carries), 3 keyframe index (no entries since the
- * index runs inside the ingest kernel), 4 the stream-statistics kernel (recorded only at
- * EDGPU_TIMING_ALL).  Up to 256 launches are kept; the history is cleared after reading.  Syncs. */
+ * index runs inside the ingest kernel), 4 the stream-statistics kernel, 5 a tap drain's kernels
+ * (4 and 5 recorded only at EDGPU_TIMING_ALL).  Up to 256 launches are kept; the history is
+ * cleared after reading.  Syncs. */
 int  edgpu_kernel_times(edgpu_ctx* ctx, int which, float* out_ms, uint32_t max_n, uint32_t* out_n);
 
 /* Which per-launch timing events the context records from now on (default EDGPU_TIMING_ALL).

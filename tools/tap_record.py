@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""Records H.264 elementary streams from the engine's taps (edgpu_tap_*).
+
+Replays a trace file (--trace, the pushes of an .edtr trace) or a small synthetic push (--sessions
+sessions of one H.264 track plus audio, --seconds long), taps every H.264 track, drains every
+tick and writes <session>_<track>_<n>.h264 (Annex-B) under --out with index.json, the units of
+every file.  A file starts at the first KEY unit and a new file is cut at the first KEY unit
+--segment seconds after the file began: the reference recorder's rule (its segment is 300 s).
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from easydarwin_amd import edgpu  # noqa: E402
+from easydarwin_amd.synth import SEED_BASE, TrackSpec, make_sdp, session_packets  # noqa: E402
+
+
+class Recorder:
+    def __init__(self, out_dir, segment_ms):
+        self.out_dir, self.segment_ms = out_dir, segment_ms
+        self.open = {}              # (session, track) -> [file object, entry, start arrival]
+        self.files = []
+        self.drained_units = 0
+
+    def take(self, data, units, streams):
+        self.drained_units += len(units)
+        for st in streams:
+            key = (int(st["session"]), int(st["track"]))
+            for u in units[int(st["unit_first"]):int(st["unit_first"]) + int(st["unit_count"])]:
+                cur = self.open.get(key)
+                is_key = bool(int(u["flags"]) & edgpu.TAP_KEY)
+                if is_key and (cur is None or int(u["arrival_ms"]) - cur[2] >= self.segment_ms):
+                    if cur:
+                        cur[0].close()
+                    name = "%d_%d_%d.h264" % (key[0], key[1], sum(1 for f in self.files if f["stream"] == list(key)))
+                    entry = {"file": name, "stream": list(key), "units": []}
+                    self.files.append(entry)
+                    cur = self.open[key] = [open(os.path.join(self.out_dir, name), "wb"), entry, int(u["arrival_ms"])]
+                if cur is None:
+                    continue                                        # nothing before the first key frame
+                off, n = int(u["offset"]), int(u["bytes"])
+                cur[1]["units"].append({"offset": cur[0].tell(), "bytes": n, "rtp_ts": int(u["rtp_ts"]),
+                                        "arrival_ms": int(u["arrival_ms"]), "flags": int(u["flags"])})
+                cur[0].write(data[off:off + n].tobytes())
+
+    def close(self):
+        for cur in self.open.values():
+            cur[0].close()
+        with open(os.path.join(self.out_dir, "index.json"), "w") as f:
+            json.dump({"files": self.files, "drained_units": self.drained_units}, f)
+
+
+def synthetic(nsessions, seconds):
+    tracks = [TrackSpec("video", "H264/90000", 96, bitrate=1_000_000, gop=30, idr_bytes=20_000),
+              TrackSpec("audio", "PCMA/8000", 8)]
+    sdps = [make_sdp(tracks)] * nsessions
+    pushes = [session_packets(tracks, seconds * 1000, SEED_BASE + i) for i in range(nsessions)]
+    return sdps, pushes
+
+
+def from_trace(path):
+    from easydarwin_amd import trace
+    tr = trace.Trace.from_bytes(open(path, "rb").read())
+    pushes = [[] for _ in tr.sdps]
+    for ev in tr.events:                    # the pushed packets only: sessions live for the whole trace here
+        if ev[0] == trace.PKT:
+            _, t, s, ch, data = ev
+            pushes[s].append((t, ch, data))
+    return list(tr.sdps), pushes
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--trace")
+    ap.add_argument("--sessions", type=int, default=2)
+    ap.add_argument("--seconds", type=int, default=3)
+    ap.add_argument("--tick-ms", type=int, default=100)
+    ap.add_argument("--segment", type=float, default=300.0, help="seconds per file")
+    ap.add_argument("--out", required=True)
+    a = ap.parse_args()
+    os.makedirs(a.out, exist_ok=True)
+    sdps, pushes = from_trace(a.trace) if a.trace else synthetic(a.sessions, a.seconds)
+    rec = Recorder(a.out, int(a.segment * 1000))
+    with edgpu.Context(max_batch_packets=1 << 15, max_batch_bytes=32 << 20, out_arena_bytes=32 << 20,
+                       max_out_packets=1 << 16) as ctx:
+        sess = []
+        for sdp in sdps:
+            s = ctx.session_add(sdp)
+            sess.append(s)
+            for t in range(ctx.session_tracks(s)):
+                try:
+                    ctx.tap_enable(s, t)
+                except edgpu.EdgpuError as e:
+                    if e.code != edgpu.BAD_ARGUMENT:
+                        raise                                       # (not an H.264 track)
+        merged = sorted(((t, i, ch, d) for i, pk in enumerate(pushes) for t, ch, d in pk), key=lambda x: x[0])
+        end = merged[-1][0] + 1 if merged else 0
+        k = 0
+        for tick in range(0, end + a.tick_ms, a.tick_ms):
+            batch = []
+            while k < len(merged) and merged[k][0] < tick + a.tick_ms:
+                t, i, ch, d = merged[k]
+                batch.append((sess[i], ch, t, d))
+                k += 1
+            if batch:
+                ctx.ingest_host(*edgpu.build_batch(batch))
+                ctx.keyframe_index()
+            rec.take(*ctx.tap_drain(flush=tick + a.tick_ms > end))
+    rec.close()
+    print(json.dumps({"files": len(rec.files), "units": rec.drained_units}))
+
+
+if __name__ == "__main__":
+    main()
