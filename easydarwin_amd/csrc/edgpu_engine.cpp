@@ -293,9 +293,10 @@ struct edgpu_ctx {
     // (ring 4, the stream-statistics kernel: its events are created by the first
     // edgpu_stream_stats_enable)
     // (ring 5, a tap drain's kernels: by the first edgpu_tap_enable)
-    hipEvent_t hist[6][kHist][2] = {};
-    uint32_t hist_n[6] = {0, 0, 0, 0, 0, 0};   // pairs recorded (monotonic sequence numbers)
-    uint32_t hist_rd[6] = {0, 0, 0, 0, 0, 0};  // pairs already returned by edgpu_kernel_times
+    // (ring 6, a transport-stream mux's kernels: by the first edgpu_ts_mux)
+    hipEvent_t hist[7][kHist][2] = {};
+    uint32_t hist_n[7] = {0, 0, 0, 0, 0, 0, 0};   // pairs recorded (monotonic sequence numbers)
+    uint32_t hist_rd[7] = {0, 0, 0, 0, 0, 0, 0};  // pairs already returned by edgpu_kernel_times
     // Borrowed end points.  A whole-tick entry (ring 1) ends at its copy kernel's end event
     // (ring 0 sequence number in tick_end[slot]); a keyframe entry (ring 3) starts at the end
     // event of the ingest it indexes (ring 2 sequence number in kf_from[slot]) when nothing ran
@@ -304,7 +305,7 @@ struct edgpu_ctx {
     static const uint32_t kOwnStart = 0xFFFFFFFFu;
     uint32_t tick_end[kHist] = {};
     uint32_t kf_from[kHist] = {};
-    uint32_t last_seq[6] = {0, 0, 0, 0, 0, 0}; // each ring's newest complete pair (edgpu_last_timings)
+    uint32_t last_seq[7] = {0, 0, 0, 0, 0, 0, 0}; // each ring's newest complete pair (edgpu_last_timings)
     bool kf_share = false;                  // the last ingest's end event may start the keyframe entry
     uint64_t fanout_launches = 0;
     int64_t last_now = 0;               // clock of the last edgpu_fanout (backpressure reports)
@@ -346,6 +347,16 @@ struct edgpu_ctx {
     DevVec<edgpu_tap_unit> d_tap_units;
     DevVec<edgpu_tap_stream> d_tap_streams;
     TapPlace* d_tap_place = nullptr;
+    // the transport-stream mux (edgpu_ts_mux): staging only, allocated by the first call; the state
+    // between calls is the caller's
+    DevVec<uint8_t> d_ts_es, d_ts_out;
+    DevVec<edgpu_tap_unit> d_ts_units_in;
+    DevVec<TsRange> d_ts_ranges;
+    DevVec<edgpu_ts_state> d_ts_states;     // 2 x n_streams: the caller's rows, the new rows
+    DevVec<TsRec> d_ts_recs;
+    DevVec<uint32_t> d_ts_base;
+    DevVec<edgpu_ts_unit> d_ts_rows;
+    uint8_t* d_ts_fixed = nullptr;          // TsPlace, then the PAT and PMT packet templates
     DevVec<SubDev> d_subs;
     DevVec<uint32_t> d_sub_index;
     DevVec<uint32_t> d_sub_range;
@@ -662,6 +673,9 @@ int edgpu_ctx_destroy(edgpu_ctx* x) {
     x->d_taps.release(); x->d_tap_list.release(); x->d_tap_items.release(); x->d_tap_out.release();
     x->d_tap_units.release(); x->d_tap_streams.release();
     if (x->d_tap_place) (void)hipFree(x->d_tap_place);
+    x->d_ts_es.release(); x->d_ts_out.release(); x->d_ts_units_in.release(); x->d_ts_ranges.release();
+    x->d_ts_states.release(); x->d_ts_recs.release(); x->d_ts_base.release(); x->d_ts_rows.release();
+    if (x->d_ts_fixed) (void)hipFree(x->d_ts_fixed);
     x->d_carry.release(); x->d_tcp_groups.release(); x->d_tcp_reads.release(); x->d_tcp_chunk_group.release();
     x->d_tcp_ncand.release(); x->d_tcp_cands.release(); x->d_tcp_links.release(); x->d_tcp_chunkres.release();
     x->d_tcp_results.release(); x->d_tcp_offs.release(); x->d_tcp_stage.release(); x->d_blocked.release();
@@ -2617,8 +2631,147 @@ int edgpu_tap_drain(edgpu_ctx* x, uint32_t flags, void* out, uint64_t out_cap, i
     return EDGPU_OK;
 }
 
+// ---- MPEG-2 transport-stream mux of tapped access units (edgpu_ts_mux; edgpu_ts.hip) ----
+static uint32_t crc32_mpeg2(const uint8_t* p, size_t n) {
+    uint32_t crc = 0xFFFFFFFFu;
+    for (size_t i = 0; i < n; i++) {
+        crc ^= (uint32_t)p[i] << 24;
+        for (int b = 0; b < 8; b++) crc = (crc & 0x80000000u) ? (crc << 1) ^ 0x04C11DB7u : crc << 1;
+    }
+    return crc;
+}
+// A PSI packet with continuity counter 0: header, pointer field, the section and its CRC, FF fill
+static void ts_psi_packet(uint8_t* pkt, uint32_t pid, const uint8_t* section, size_t n) {
+    memset(pkt, 0xFF, EDGPU_TS_PACKET);
+    pkt[0] = 0x47; pkt[1] = (uint8_t)(0x40 | (pid >> 8)); pkt[2] = (uint8_t)pid; pkt[3] = 0x10; pkt[4] = 0x00;
+    memcpy(pkt + 5, section, n);
+    const uint32_t crc = crc32_mpeg2(section, n);
+    for (int i = 0; i < 4; i++) pkt[5 + n + i] = (uint8_t)(crc >> (24 - 8 * i));
+}
+
+int edgpu_ts_mux(edgpu_ctx* x, const edgpu_ts_config* cfg, const void* es, uint64_t es_bytes, int es_kind,
+                 const edgpu_tap_unit* units, uint32_t n_units, const edgpu_tap_stream* streams, uint32_t n_streams,
+                 edgpu_ts_state* states, void* out, uint64_t out_cap, int out_kind, edgpu_ts_unit* ts_units,
+                 edgpu_ts_result* result) {
+    if (!x || !result || (!es && es_bytes) || (!out && out_cap) || (!units && n_units) || (!ts_units && n_units) ||
+        (!streams && n_streams) || (!states && n_streams))
+        return fail(EDGPU_BAD_ARGUMENT, "bad argument");
+    for (int k : {es_kind, out_kind})
+        if (k != EDGPU_PTR_HOST && k != EDGPU_PTR_DEVICE && k != EDGPU_PTR_PINNED) return fail(EDGPU_BAD_ARGUMENT, "bad pointer kind");
+    const bool device_es = es_kind == EDGPU_PTR_DEVICE, device_out = out_kind == EDGPU_PTR_DEVICE;
+    if ((device_es && ((uintptr_t)es & 15)) || (device_out && ((uintptr_t)out & 15)))
+        return fail(EDGPU_BAD_ARGUMENT, "device `es` and `out` must be 16-B aligned");
+    edgpu_ts_config c;
+    memset(&c, 0, sizeof(c));
+    if (cfg) c = *cfg;
+    if (!c.pmt_pid) c.pmt_pid = 0x1000;
+    if (!c.video_pid) c.video_pid = 0x0100;
+    if (!c.tsid) c.tsid = 1;
+    if (!c.program) c.program = 1;
+    if (!c.flags) c.flags = EDGPU_TS_AUD;
+    if (!c.pcr_lead) c.pcr_lead = 63000;
+    if (c.pmt_pid > 0x1FFF || c.video_pid > 0x1FFF || c.pmt_pid == c.video_pid || (c.flags & ~(EDGPU_TS_AUD | EDGPU_TS_NOAUD)))
+        return fail(EDGPU_BAD_ARGUMENT, "bad transport-stream configuration");
+    // the rows the kernels index by: checked here, on the host
+    std::vector<TsRange> ranges(n_streams);
+    uint64_t covered = 0, next = 0;
+    for (uint32_t s = 0; s < n_streams; s++) {
+        const uint64_t first = streams[s].unit_first, count = streams[s].unit_count;
+        if (first + count > n_units) return fail(EDGPU_BAD_ARGUMENT, "a stream's unit range reaches outside the units");
+        if (count) {
+            if (first < next) return fail(EDGPU_BAD_ARGUMENT, "the streams' unit ranges must ascend without overlap");
+            next = first + count;
+        }
+        ranges[s] = TsRange{(uint32_t)first, (uint32_t)count};
+        covered += count;
+    }
+    for (uint32_t i = 0; i < n_units; i++) {
+        if (units[i].stream >= n_streams) return fail(EDGPU_BAD_ARGUMENT, "a unit's stream index is out of range");
+        if (units[i].offset > es_bytes || units[i].bytes > es_bytes - units[i].offset)
+            return fail(EDGPU_BAD_ARGUMENT, "a unit reaches outside the ES bytes");
+    }
+    memset(result, 0, sizeof(*result));
+    result->units = n_units; result->streams = n_streams;
+    if (!n_streams) {
+        if (n_units) memset(ts_units, 0, (size_t)n_units * sizeof(edgpu_ts_unit));
+        return EDGPU_OK;
+    }
+    DEVICE_ENTER(x);
+    if (!x->hist[6][0][0])
+        for (auto& s : x->hist[6]) for (auto& e : s) HIP_CHECK(hipEventCreate(&e));
+    constexpr size_t kTmplOff = 16;
+    if (!x->d_ts_fixed && dmalloc(&x->d_ts_fixed, kTmplOff + 2 * EDGPU_TS_PACKET) != hipSuccess)
+        return fail(EDGPU_OUT_OF_MEMORY, "transport-stream mux staging");
+    uint8_t tmpl[2 * EDGPU_TS_PACKET];
+    {
+        const uint8_t pat[12] = {0x00, 0xB0, 0x0D, (uint8_t)(c.tsid >> 8), (uint8_t)c.tsid, 0xC1, 0x00, 0x00,
+                                 (uint8_t)(c.program >> 8), (uint8_t)c.program, (uint8_t)(0xE0 | (c.pmt_pid >> 8)), (uint8_t)c.pmt_pid};
+        const uint8_t vh = (uint8_t)(0xE0 | (c.video_pid >> 8)), vl = (uint8_t)c.video_pid;
+        const uint8_t pmt[17] = {0x02, 0xB0, 0x12, (uint8_t)(c.program >> 8), (uint8_t)c.program, 0xC1, 0x00, 0x00,
+                                 vh, vl, 0xF0, 0x00, 0x1B, vh, vl, 0xF0, 0x00};
+        ts_psi_packet(tmpl, 0, pat, sizeof(pat));
+        ts_psi_packet(tmpl + EDGPU_TS_PACKET, c.pmt_pid, pmt, sizeof(pmt));
+    }
+    HIP_CHECK(x->d_ts_units_in.reserve(std::max<uint32_t>(n_units, 1), x->stream));
+    HIP_CHECK(x->d_ts_recs.reserve(std::max<uint32_t>(n_units, 1), x->stream));
+    HIP_CHECK(x->d_ts_rows.reserve(std::max<uint32_t>(n_units, 1), x->stream));
+    HIP_CHECK(x->d_ts_ranges.reserve(n_streams, x->stream));
+    HIP_CHECK(x->d_ts_states.reserve(2 * (size_t)n_streams, x->stream));
+    HIP_CHECK(x->d_ts_base.reserve((size_t)n_streams + 1, x->stream));
+    if (!device_es) HIP_CHECK(x->d_ts_es.reserve(es_bytes + 16, x->stream));
+    // staging for the most the units can need (three packets of PSI and header overhead each), so
+    // that a call with room plans once
+    if (!device_out)
+        HIP_CHECK(x->d_ts_out.reserve(std::min<uint64_t>(out_cap, (4ull * n_units + es_bytes / 184 + 1) * EDGPU_TS_PACKET), x->stream));
+    HIP_CHECK(hipMemcpyAsync(x->d_ts_fixed + kTmplOff, tmpl, sizeof(tmpl), hipMemcpyHostToDevice, x->stream));
+    if (n_units) HIP_CHECK(hipMemcpyAsync(x->d_ts_units_in.ptr, units, (size_t)n_units * sizeof(edgpu_tap_unit), hipMemcpyHostToDevice, x->stream));
+    HIP_CHECK(hipMemcpyAsync(x->d_ts_ranges.ptr, ranges.data(), (size_t)n_streams * sizeof(TsRange), hipMemcpyHostToDevice, x->stream));
+    HIP_CHECK(hipMemcpyAsync(x->d_ts_states.ptr, states, (size_t)n_streams * sizeof(edgpu_ts_state), hipMemcpyHostToDevice, x->stream));
+    if (!device_es && es_bytes) HIP_CHECK(hipMemcpyAsync(x->d_ts_es.ptr, es, es_bytes, hipMemcpyHostToDevice, x->stream));
+    if (covered != n_units) HIP_CHECK(hipMemsetAsync(x->d_ts_recs.ptr, 0, (size_t)n_units * sizeof(TsRec), x->stream));
+    HIP_CHECK(wsync(x, x->stream));             // `tmpl` and `ranges` are on the stack
+    TsPlace pl;
+    for (int attempt = 0;; attempt++) {
+        TsParams p;
+        p.es = device_es ? (const uint8_t*)es : x->d_ts_es.ptr;
+        p.units = x->d_ts_units_in.ptr; p.ranges = x->d_ts_ranges.ptr;
+        p.states = x->d_ts_states.ptr; p.new_states = x->d_ts_states.ptr + n_streams;
+        p.recs = x->d_ts_recs.ptr; p.base = x->d_ts_base.ptr;
+        p.place = reinterpret_cast<TsPlace*>(x->d_ts_fixed);
+        p.tmpl = reinterpret_cast<const uint32_t*>(x->d_ts_fixed + kTmplOff);
+        p.out = device_out ? (uint8_t*)out : x->d_ts_out.ptr;
+        p.ts_units = x->d_ts_rows.ptr;
+        p.out_cap = device_out ? out_cap : std::min<uint64_t>(out_cap, x->d_ts_out.cap);
+        p.pts_offset = c.pts_offset;
+        p.n_units = n_units; p.n_streams = n_streams;
+        p.pcr_lead = c.pcr_lead; p.video_pid = c.video_pid;
+        p.aud = (c.flags & EDGPU_TS_AUD) ? 1u : 0u;
+        HIP_CHECK(hist_mark(x, 6, 0));
+        HIP_CHECK(launch_ts_mux(p, (uint32_t)std::max(x->num_cus * 8, 1), x->stream));
+        HIP_CHECK(hist_mark(x, 6, 1));
+        {
+            Readback rb(x);
+            HIP_CHECK(rb.add(&pl, x->d_ts_fixed, sizeof(pl)));
+            HIP_CHECK(rb.run());
+        }
+        if (pl.commit) break;
+        result->bytes = pl.bytes;
+        if (pl.bytes > out_cap || attempt || device_out)
+            return fail(EDGPU_OUT_OVERFLOW, "transport-stream mux: " + std::to_string(pl.bytes) + " bytes needed; nothing was written");
+        // the caller has room, the context's staging did not: grown, and the mux made again
+        HIP_CHECK(x->d_ts_out.reserve(pl.bytes, x->stream));
+    }
+    result->bytes = pl.bytes;
+    Readback rb(x);
+    if (!device_out) HIP_CHECK(rb.add(out, x->d_ts_out.ptr, pl.bytes));
+    HIP_CHECK(rb.add(ts_units, x->d_ts_rows.ptr, (size_t)n_units * sizeof(edgpu_ts_unit)));
+    HIP_CHECK(rb.add(states, x->d_ts_states.ptr + n_streams, (size_t)n_streams * sizeof(edgpu_ts_state)));
+    HIP_CHECK(rb.run());
+    return EDGPU_OK;
+}
+
 int edgpu_kernel_times(edgpu_ctx* x, int which, float* out_ms, uint32_t max_n, uint32_t* out_n) {
-    if (!x || which < 0 || which > 5 || (!out_ms && max_n)) return fail(EDGPU_BAD_ARGUMENT, "bad argument");
+    if (!x || which < 0 || which > 6 || (!out_ms && max_n)) return fail(EDGPU_BAD_ARGUMENT, "bad argument");
     DEVICE_ENTER(x);
     HIP_CHECK(sync_all(x));
     const uint32_t n = std::min<uint32_t>(x->hist_n[which] - x->hist_rd[which], edgpu_ctx::kHist);

@@ -246,6 +246,44 @@ struct TapParams {
 };
 hipError_t launch_tap_drain(const TapParams& p, uint32_t copy_blocks, hipStream_t st);
 
+// The transport-stream mux (edgpu_ts_mux, edgpu_ts.hip): k_ts_plan (a wave per stream row),
+// k_ts_place (one workgroup) and k_ts_pack (flat over the output's 16-B words).
+struct TsRec {                  // what k_ts_plan leaves per unit for k_ts_pack; zero for a unit no row covers
+    uint64_t pts;               // 33 bits
+    uint32_t pk;                // its first packet, relative to the stream's
+    uint32_t npk;               // its packets, PAT / PMT included
+    uint32_t misc;              // cc_video | cc_pat << 4 | cc_pmt << 8 | key << 12 | aud << 13 of its first packets
+    uint32_t stream;
+    uint32_t flags, _pad;       // the tap unit's
+};
+static_assert(sizeof(TsRec) == 32, "TsRec layout");
+struct TsRange { uint32_t first, count; };
+struct TsPlace {                // k_ts_place's verdict
+    uint64_t bytes;
+    uint32_t packets;
+    uint32_t commit;
+};
+struct TsParams {
+    const uint8_t* es;
+    const edgpu_tap_unit* units;
+    const TsRange* ranges;      // per stream row: its units
+    const edgpu_ts_state* states;
+    edgpu_ts_state* new_states;
+    TsRec* recs;                // n_units
+    uint32_t* base;             // n_streams + 1: k_ts_plan leaves each stream's packets, k_ts_place their exclusive sums
+    TsPlace* place;
+    const uint32_t* tmpl;       // PAT and PMT packets, 47 words each
+    uint8_t* out;
+    edgpu_ts_unit* ts_units;
+    uint64_t out_cap;
+    uint64_t pts_offset;
+    uint32_t n_units, n_streams;
+    uint32_t pcr_lead;
+    uint32_t video_pid;
+    uint32_t aud;
+};
+hipError_t launch_ts_mux(const TsParams& p, uint32_t pack_blocks, hipStream_t st);
+
 struct ImageParams {
     SenderDev* senders;
     SessionDev* sessions;

@@ -56,6 +56,7 @@
 #include <mutex>
 #include <thread>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "edgpu.h"
@@ -195,6 +196,12 @@ public:
     int  EnableElementaryStream(uint32_t session, uint32_t track);
     int  DisableElementaryStream(uint32_t session, uint32_t track);
     int  DrainElementaryStreams(const TapSink& sink, bool flush = false);
+    // The same drain muxed into an MPEG-2 transport stream on the GPU (edgpu_ts_mux): `sink` gets, per
+    // stream, its row, one edgpu_ts_unit per drained unit (offsets relative to `packets`) and the
+    // 188-byte packets.  The mux's state rows are held here by (session, track) and dropped by
+    // DisableElementaryStream.
+    typedef std::function<void(const edgpu_tap_stream& stream, const edgpu_ts_unit* units, const uint8_t* packets)> TsSink;
+    int  DrainTransportStreams(const TsSink& sink, bool flush = false, const edgpu_ts_config* cfg = nullptr);
     // diagnostics: one wave on the engine stream waits `us` of the device clock (edgpu_debug_stall)
     int DebugStall(uint32_t us);
     // the message of the last ReflectPackets failure that happened on another thread than the
@@ -215,6 +222,7 @@ private:
     // thread's hold of fEngineMu, given up during writes when fConcurrent; fDelivering is true from
     // a tick's first write to its backpressure report (waiters: fIdleCv on fEngineMu)
     std::mutex fEngineMu;
+    std::vector<std::pair<uint64_t, edgpu_ts_state>> fTsStates;   // by session << 32 | track: DrainTransportStreams (fEngineMu)
     std::vector<uint8_t> fStatsOn;                          // per session: EnableStreamStats (fEngineMu)
     uint32_t fNumStats = 0;
     int (*fSampleStats)(edgpu_ctx*, int64_t) = nullptr;     // edgpu_stream_stats_sample once enabled

@@ -46,7 +46,7 @@ EXPORTED = [
     "edgpu_ipc_export", "edgpu_ipc_open", "edgpu_ipc_close", "edgpu_copy_to_device",
     "edgpu_stream_stats_enable", "edgpu_stream_stats_disable", "edgpu_stream_stats_sample",
     "edgpu_stream_stats_get", "edgpu_session_bitrate",
-    "edgpu_tap_enable", "edgpu_tap_disable", "edgpu_tap_drain",
+    "edgpu_tap_enable", "edgpu_tap_disable", "edgpu_tap_drain", "edgpu_ts_mux",
 ]
 IPC_HANDLE_BYTES = 64
 TCP_MESSAGE, TCP_DROPPED = 1, 2
@@ -194,17 +194,45 @@ class TapResult(C.Structure):
     _fields_ = [("bytes", C.c_uint64), ("units", C.c_uint32), ("streams", C.c_uint32)]
 
 
+class TsConfig(C.Structure):
+    """edgpu_ts_config: a field that is 0 takes its default."""
+    _fields_ = [("pmt_pid", C.c_uint16), ("video_pid", C.c_uint16), ("tsid", C.c_uint16), ("program", C.c_uint16),
+                ("flags", C.c_uint32), ("pcr_lead", C.c_uint32), ("pts_offset", C.c_uint64)]
+
+
+class TsState(C.Structure):
+    """edgpu_ts_state: what the mux carries per stream between calls; the caller holds it."""
+    _fields_ = [("ext_ts", C.c_uint64), ("started", C.c_uint8), ("cc_pat", C.c_uint8), ("cc_pmt", C.c_uint8),
+                ("cc_video", C.c_uint8), ("_pad", C.c_uint32)]
+
+
+class TsUnit(C.Structure):
+    """edgpu_ts_unit: where one input unit's transport-stream packets are."""
+    _fields_ = [("offset", C.c_uint64), ("bytes", C.c_uint32), ("flags", C.c_uint32), ("pts", C.c_uint64),
+                ("stream", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class TsResult(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("units", C.c_uint32), ("streams", C.c_uint32)]
+
+
+TS_AUD, TS_NOAUD = 1, 2
+TS_PACKET = 188
+
 TAP_KEY, TAP_PARAMS, TAP_DAMAGED, TAP_NOMARKER, TAP_OPEN_END = 1, 2, 4, 8, 16
 TAP_FLUSH = 1
 TAP_ROUND = 64              # EDGPU_TAP_ROUND: queue entries per round of the scan kernel
 
 # numpy mirrors (same layout as the C structs)
-_NP_OF = {C.c_uint32: "<u4", C.c_uint64: "<u8", C.c_int64: "<i8"}
+_NP_OF = {C.c_uint32: "<u4", C.c_uint64: "<u8", C.c_int64: "<i8", C.c_uint8: "u1"}
 STREAM_STATS_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in StreamStats._fields_])
 assert STREAM_STATS_DTYPE.itemsize == C.sizeof(StreamStats) == 176
 TAP_UNIT_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in TapUnit._fields_])
 TAP_STREAM_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in TapStream._fields_])
 assert TAP_UNIT_DTYPE.itemsize == C.sizeof(TapUnit) == 48 and TAP_STREAM_DTYPE.itemsize == C.sizeof(TapStream) == 96
+TS_UNIT_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in TsUnit._fields_])
+TS_STATE_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in TsState._fields_])
+assert TS_UNIT_DTYPE.itemsize == C.sizeof(TsUnit) == 32 and TS_STATE_DTYPE.itemsize == C.sizeof(TsState) == 16
 PKT_DTYPE = np.dtype([("slot", "<u4"), ("len", "<u2"), ("channel", "u1"), ("flags", "u1"),
                       ("arrival_ms", "<i8")])
 OUT_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u4"), ("packet_id", "<u4")])
@@ -328,6 +356,7 @@ def load(path: str = LIB_PATH):
         "edgpu_tap_enable": (I32, [P, U32, U32]),
         "edgpu_tap_disable": (I32, [P, U32, U32]),
         "edgpu_tap_drain": (I32, [P, U32, P, U64, I32, P, U32, P, U32, C.POINTER(TapResult)]),
+        "edgpu_ts_mux": (I32, [P, C.POINTER(TsConfig), P, U64, I32, P, U32, P, U32, P, P, U64, I32, P, C.POINTER(TsResult)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -416,6 +445,8 @@ class Context:
         down with it (kill_clients_when_broadcast_stops)."""
         _check(self.lib.edgpu_session_remove(self.h, session, SESSION_KILL_OUTPUTS if kill_outputs else 0))
         self._ntracks.pop(session, None)
+        for k in [k for k in getattr(self, "_ts_states", {}) if k[0] == session]:
+            del self._ts_states[k]
 
     def subscriber_add(self, session: int, transport: int = TRANSPORT_UDP) -> int:
         out = C.c_uint32()
@@ -608,6 +639,7 @@ class Context:
 
     def tap_disable(self, session: int, track: int):
         _check(self.lib.edgpu_tap_disable(self.h, session, track))
+        getattr(self, "_ts_states", {}).pop((session, track), None)
 
     def tap_drain_raw(self, flags, out_ptr, out_cap, ptr_kind, units: np.ndarray, streams: np.ndarray) -> tuple:
         """edgpu_tap_drain as it is: (status, TapResult)."""
@@ -640,6 +672,63 @@ class Context:
         data = buf[:res.bytes] if buf is not None else int(res.bytes)
         return data, units[:res.units], streams[:res.streams]
 
+    def ts_mux_raw(self, cfg, es_ptr, es_bytes, es_kind, units: np.ndarray, streams: np.ndarray, states: np.ndarray,
+                   out_ptr, out_cap, out_kind, ts_units: np.ndarray) -> tuple:
+        """edgpu_ts_mux as it is: (status, TsResult).  `units` / `streams` are TAP_UNIT_DTYPE /
+        TAP_STREAM_DTYPE rows, `states` TS_STATE_DTYPE rows (in / out), `ts_units` TS_UNIT_DTYPE rows."""
+        res = TsResult()
+        rc = self.lib.edgpu_ts_mux(self.h, C.byref(cfg) if cfg is not None else None, C.c_void_p(es_ptr), es_bytes, es_kind,
+                                   _ptr(units) if len(units) else None, len(units),
+                                   _ptr(streams) if len(streams) else None, len(streams),
+                                   _ptr(states) if len(states) else None,
+                                   C.c_void_p(out_ptr), out_cap, out_kind,
+                                   _ptr(ts_units) if len(ts_units) else None, C.byref(res))
+        return rc, res
+
+    def tap_drain_ts(self, flush: bool = False, cfg=None):
+        """Drains every enabled tap into device memory and muxes the units into an MPEG-2 transport
+        stream there (edgpu_tap_drain, edgpu_ts_mux): (ts_bytes, ts_units, streams) -- a uint8 array
+        of 188-byte packets, TS_UNIT_DTYPE rows (one per drained unit) and the drain's
+        TAP_STREAM_DTYPE rows.  The mux's state rows are kept here by (session, track); tap_disable
+        and session_remove drop them."""
+        if not hasattr(self, "_ts_states"):
+            self._ts_states = {}
+        if getattr(self, "_ts_es", None) is None:
+            self._ts_es = self.device_alloc(1 << 20)
+        caps = getattr(self, "_tap_caps", [1 << 20, 4096, 64])
+        for attempt in range(2):
+            units = np.zeros(caps[1], dtype=TAP_UNIT_DTYPE)
+            streams = np.zeros(caps[2], dtype=TAP_STREAM_DTYPE)
+            rc, res = self.tap_drain_raw(TAP_FLUSH if flush else 0, self._ts_es.ptr, self._ts_es.nbytes, PTR_DEVICE, units, streams)
+            if rc != OUT_OVERFLOW or attempt:
+                break
+            caps = [caps[0], max(caps[1], int(res.units)), max(caps[2], int(res.streams))]
+            self._tap_caps = caps
+            if res.bytes > self._ts_es.nbytes:
+                self._ts_es.free()
+                self._ts_es = None
+                self._ts_es = self.device_alloc(max(int(res.bytes), 2 * caps[0]))
+        _check(rc)
+        units, streams = units[:res.units], streams[:res.streams]
+        keys = [(int(st["session"]), int(st["track"])) for st in streams]
+        states = np.zeros(len(streams), dtype=TS_STATE_DTYPE)
+        for i, k in enumerate(keys):
+            if k in self._ts_states:
+                states[i] = self._ts_states[k]
+        ts_units = np.zeros(len(units), dtype=TS_UNIT_DTYPE)
+        cap = getattr(self, "_ts_cap", 1 << 20)
+        for attempt in range(2):
+            out = np.empty(cap, dtype=np.uint8)
+            rc, tres = self.ts_mux_raw(cfg, self._ts_es.ptr, int(res.bytes), PTR_DEVICE, units, streams, states,
+                                       out.ctypes.data, out.nbytes, PTR_HOST, ts_units)
+            if rc != OUT_OVERFLOW or attempt:
+                break
+            cap = self._ts_cap = max(int(tres.bytes), 2 * cap)
+        _check(rc)
+        for i, k in enumerate(keys):
+            self._ts_states[k] = states[i].copy()
+        return out[:tres.bytes], ts_units, streams
+
     def debug_stall(self, us: int):
         """edgpu_debug_stall: one wave on the context stream waits `us` microseconds of the device
         clock -- work the GPU watchdog (watchdog_ms) can time out on."""
@@ -667,7 +756,8 @@ class Context:
         _check(self.lib.edgpu_set_timing(self.h, level))
 
     def kernel_times(self, which: int) -> list:
-        """which: 0 fan-out kernel, 1 whole fan-out tick, 2 ingest, 3 keyframe index, 4 stream statistics."""
+        """which: 0 fan-out kernel, 1 whole fan-out tick, 2 ingest, 3 keyframe index, 4 stream statistics,
+        5 a tap drain, 6 a transport-stream mux."""
         buf = (C.c_float * 256)()
         n = C.c_uint32()
         _check(self.lib.edgpu_kernel_times(self.h, which, buf, 256, C.byref(n)))

@@ -873,7 +873,8 @@ int  edgpu_session_bitrate(edgpu_ctx* ctx, uint32_t session, uint32_t* bps);
  * Between drains a tap carries its head, the previous good packet's sequence number, a
  * pending-damage bit and the counters.  Taps belong to the owning context: they do not travel in
  * session images, a replica session starts without them, edgpu_session_remove clears them.
- * Out of scope: MP4 / TS muxing, audio, packetization-mode 2, H.265, reordering. */
+ * Out of scope: MP4 muxing, audio, packetization-mode 2, H.265, reordering.  (The drained units as
+ * an MPEG-2 transport stream: edgpu_ts_mux below.) */
 #define EDGPU_TAP_KEY       1u
 #define EDGPU_TAP_PARAMS    2u
 #define EDGPU_TAP_DAMAGED   4u
@@ -925,11 +926,96 @@ int  edgpu_tap_drain(edgpu_ctx* ctx, uint32_t flags, void* out, uint64_t out_cap
                      edgpu_tap_unit* units, uint32_t unit_cap, edgpu_tap_stream* streams, uint32_t stream_cap,
                      edgpu_tap_result* result);
 
+/* ---- MPEG-2 transport-stream mux of tapped access units ----
+ *
+ * edgpu_ts_mux turns what edgpu_tap_drain returned -- the Annex-B bytes, the unit rows, the stream
+ * rows -- into 188-byte transport-stream packets on the GPU: what an HLS segmenter cuts into .ts
+ * files (easydarwin_amd/hls.py).  Between calls it depends only on one edgpu_ts_state row per
+ * stream, which the caller holds (zero to start): the context keeps no table and there is nothing
+ * to enable or disable.  Nothing is launched or allocated until the first call.
+ * tests/ts_model.py is the executable statement of the rules below.
+ *
+ * The output is one run of packets: the streams in row order, each stream's units
+ * [unit_first, unit_first + unit_count) in order.  The stream rows' ranges must ascend without
+ * overlap (as a drain yields them); a unit no row covers is not muxed and its row is zero.
+ *   PTS.  The RTP timestamp is extended per stream: the first unit ever (started == 0) has
+ *     ext = rtp_ts; after that ext = prev_ext + (int32)(rtp_ts - (uint32)prev_ext) (mod 2^64).  The
+ *     deltas are signed, so a timestamp that steps back gives a smaller PTS.
+ *     pts = (ext + pts_offset) mod 2^33.  There is no DTS: every unit is presented in decoding
+ *     order, so streams with B-frames are out of scope.  A unit with bytes == 0 emits nothing but
+ *     still advances ext (and sets started).
+ *   PES.  One per unit with ES bytes: 00 00 01 E0, PES length 00 00 (unbounded), 84 (marker bits +
+ *     data alignment), 80 (PTS only), 05, the 5-byte PTS (prefix 0010, 33 bits, three marker
+ *     bits); with EDGPU_TS_AUD in effect and the unit shorter than 5 bytes or its byte 4 (the first
+ *     NAL header) not of type 9 (& 0x1F): an access unit delimiter 00 00 00 01 09 F0; then the
+ *     unit's ES bytes.
+ *   Packets of a unit, PID video_pid.  The first has payload-unit-start and an adaptation field of
+ *     length 7: flags 0x10 (PCR), plus 0x40 (random access) on an EDGPU_TAP_KEY unit; PCR base
+ *     (ext + pts_offset - pcr_lead) mod 2^33, the six reserved bits set, extension 0.  So the first
+ *     packet carries up to 176 PES bytes, each later one up to 184.  The last packet is filled from
+ *     the front by adaptation-field stuffing: the adaptation-field length, a flags byte 00 when the
+ *     length is at least 1, then FF bytes (a remainder of exactly 183 bytes takes an adaptation
+ *     field of length 0); when the last packet is also the first, the FF bytes follow the PCR and
+ *     lengthen the first packet's adaptation field.  The 4-bit continuity counter runs through the
+ *     stream's video packets from cc_video.
+ *   PSI.  Before every EDGPU_TAP_KEY unit that has ES bytes: one PAT packet on PID 0 and one PMT
+ *     packet on pmt_pid, each with payload-unit-start, pointer field 00, FF fill and a continuity
+ *     counter of its own (cc_pat, cc_pmt).  The PAT names one program; the PMT declares stream type
+ *     0x1B on video_pid, PCR PID video_pid, no descriptors; both version 0, current.  (The host
+ *     computes the CRC-32/MPEG-2 once per call; the kernel patches the counters into two packet
+ *     templates.)  The defaults give the PAT section 00 B0 0D 00 01 C1 00 00 00 01 F0 00 2A B1 04 B2
+ *     and the PMT section 02 B0 12 00 01 C1 00 00 E1 00 F0 00 1B E1 00 F0 00 15 BD 4D 56.
+ *   A unit's row: offset and bytes of its packets (PAT / PMT included; bytes 0 for a unit without ES
+ *     bytes, offset where its packets would begin), the tap unit's flags, its pts, its stream row.
+ * Configuration: a field that is 0 takes its default, so `flags` 0 means EDGPU_TS_AUD;
+ * EDGPU_TS_NOAUD alone turns the delimiter off; pcr_lead 0 means 63000.  PIDs above 0x1FFF, equal
+ * PIDs or unknown flag bits are EDGPU_BAD_ARGUMENT.
+ * Out of scope: audio PIDs, DTS / B-frames, MP4 and fMP4, H.265, SCTE markers. */
+#define EDGPU_TS_AUD      1u
+#define EDGPU_TS_NOAUD    2u
+#define EDGPU_TS_PACKET 188u
+typedef struct edgpu_ts_config {     /* 0 in a field: the default */
+    uint16_t pmt_pid;                /* 0x1000 */
+    uint16_t video_pid;              /* 0x0100, also the PCR PID */
+    uint16_t tsid, program;          /* 1, 1 */
+    uint32_t flags;                  /* EDGPU_TS_AUD */
+    uint32_t pcr_lead;               /* 90-kHz ticks the PCR runs before the PTS; default 63000 (0.7 s) */
+    uint64_t pts_offset;             /* added to every PTS, 90 kHz */
+} edgpu_ts_config;
+typedef struct edgpu_ts_state {      /* per stream, caller-held, zero to start */
+    uint64_t ext_ts;                 /* extended RTP timestamp of the last unit muxed */
+    uint8_t  started, cc_pat, cc_pmt, cc_video;
+    uint32_t _pad;
+} edgpu_ts_state;
+typedef struct edgpu_ts_unit {       /* one per input unit, same index */
+    uint64_t offset;                 /* of its first TS packet in `out`, a multiple of 188 */
+    uint32_t bytes;                  /* 188 x its packets, PAT/PMT included; 0 for a unit with no ES bytes */
+    uint32_t flags;                  /* the tap unit's */
+    uint64_t pts;                    /* 33 bits */
+    uint32_t stream, _pad;
+} edgpu_ts_unit;
+typedef struct edgpu_ts_result { uint64_t bytes; uint32_t units, streams; } edgpu_ts_result;
+/* Muxes on the context stream and syncs.  `es` and `out` are each device memory used in place
+ * (EDGPU_PTR_DEVICE, 16-B aligned) or host memory (EDGPU_PTR_HOST / EDGPU_PTR_PINNED, through
+ * context-owned device staging that grows on demand); `units`, `streams`, `states` (n_streams rows,
+ * in / out) and `ts_units` (n_units rows) are host arrays.  EDGPU_BAD_ARGUMENT when a unit reaches
+ * outside es_bytes, a unit's `stream` is not below n_streams or a stream's unit range is out of
+ * range.  When out_cap is too small the call returns EDGPU_OUT_OVERFLOW, `result` holds what is
+ * needed, and no byte of `out`, no unit row and no state row is written: a retry with room gives
+ * what a first call would have given.  No byte at or beyond result->bytes is written. */
+int  edgpu_ts_mux(edgpu_ctx* ctx, const edgpu_ts_config* cfg /* NULL: defaults */,
+                  const void* es, uint64_t es_bytes, int es_kind,
+                  const edgpu_tap_unit* units, uint32_t n_units,
+                  const edgpu_tap_stream* streams, uint32_t n_streams,
+                  edgpu_ts_state* states /* n_streams, in/out */,
+                  void* out, uint64_t out_cap, int out_kind,
+                  edgpu_ts_unit* ts_units /* n_units */, edgpu_ts_result* result);
+
 /* Per-launch device durations (ms, HIP events on the ctx stream) recorded since the last
  * call, oldest first, for `which` = 0 fan-out copy kernel, 1 whole fan-out tick (plan +
  * copy), 2 ingest (with the keyframe index it carries), 3 keyframe index (no entries since the
- * index runs inside the ingest kernel), 4 the stream-statistics kernel, 5 a tap drain's kernels
- * (4 and 5 recorded only at EDGPU_TIMING_ALL).  Up to 256 launches are kept; the history is
+ * index runs inside the ingest kernel), 4 the stream-statistics kernel, 5 a tap drain's kernels,
+ * 6 a transport-stream mux's kernels (4, 5 and 6 recorded only at EDGPU_TIMING_ALL).  Up to 256 launches are kept; the history is
  * cleared after reading.  Syncs. */
 int  edgpu_kernel_times(edgpu_ctx* ctx, int which, float* out_ms, uint32_t max_n, uint32_t* out_n);
 
