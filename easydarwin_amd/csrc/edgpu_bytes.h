@@ -67,13 +67,4 @@ __device__ __forceinline__ u32x4 keep16(u32x4 v, int nb) {
     return u32x4{o[0], o[1], o[2], o[3]};
 }
 
-// Lane l gets lane l + 1's value of `v`; lane 63 gets `last` (DPP wave_shl:1, one VALU op per
-// dword -- no LDS traffic, unlike a __shfl).
-__device__ __forceinline__ u32x4 wave_next(u32x4 v, u32x4 last) {
-    return u32x4{(uint32_t)__builtin_amdgcn_update_dpp((int)last.x, (int)v.x, 0x130, 0xF, 0xF, false),
-                 (uint32_t)__builtin_amdgcn_update_dpp((int)last.y, (int)v.y, 0x130, 0xF, 0xF, false),
-                 (uint32_t)__builtin_amdgcn_update_dpp((int)last.z, (int)v.z, 0x130, 0xF, 0xF, false),
-                 (uint32_t)__builtin_amdgcn_update_dpp((int)last.w, (int)v.w, 0x130, 0xF, 0xF, false)};
-}
-
 }  // namespace edgpu

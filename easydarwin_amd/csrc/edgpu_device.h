@@ -44,15 +44,6 @@ struct PktMeta {                    // 32 B
     uint32_t vcount;                // number of non-empty packets before this one (mod 2^32)
 };
 
-struct CopyJob {                    // 32 B: one enqueued packet's slot copy, blob -> byte ring
-    uint64_t ring;                  // device pointer of the sender's byte ring (16-B words)
-    uint64_t vword;                 // virtual word index of the slot
-    uint32_t wmask;                 // ring words - 1
-    uint32_t src_slot;              // slot index in the batch blob
-    uint32_t len;                   // packet length (0: nothing to copy)
-    uint32_t sender;                // global sender index (its vbyte_end bounds the live words)
-};
-
 struct SenderDev {
     // static
     uint64_t meta;                  // device pointer to PktMeta[ring_packets]
@@ -361,14 +352,8 @@ struct TickTotals {                 // device-side, mirrors edgpu_tick_stats
     unsigned long long cum_ingested_packets;
     unsigned long long cum_ingested_bytes;
     int ingest_status;              // sticky: an ingest lapped data an in-flight fan-out reads
-    unsigned int fan_next;          // dynamic fan-out variants: next work item to claim (per tick)
+    unsigned int fan_next;          // the copy kernel's next work item to claim (per tick)
     unsigned int _pad;
-    // measurement builds: the copy kernel's workgroups' first start / first and last exit
-    // (s_memrealtime, 100 MHz) -- the tail of the dynamic schedule (EDGPU_FAN_TAIL=1 prints it)
-    unsigned long long fan_t0_min, fan_done_min, fan_done_max;
-    unsigned long long ing_t0_min, ing_done_min, ing_done_max;    // the same for k_ingest
-    unsigned long long ing_last_span, ing_last_first;             // ... of the last finished ingest
-    unsigned long long ing_ph[8], ing_last_ph[8];                 // k_ingest phase sums ([0]: segments)
     // Copy passes of an over-capacity tick (edgpu_fanout_next).  Slot k & 1 belongs to the k-th
     // launched pass: the arena bytes and descriptors its sub-streams span, and the id of the next
     // pass (kNoPass: none).  A pass's plan resets the other slot for the pass after it.

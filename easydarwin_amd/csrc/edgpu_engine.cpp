@@ -52,7 +52,6 @@ hipError_t launch_sub_active(const edgpu_substream_out* sub, uint32_t n, uint32_
 hipError_t launch_stall(uint64_t ticks, hipStream_t st);
 int fanout_chunk(int variant);
 int fanout_default(bool patching);
-bool fanout_rewrites(int variant);
 const char* fanout_name(int variant);
 }  // namespace edgpu
 
@@ -267,24 +266,17 @@ struct edgpu_ctx {
     edgpu_config cfg;
     int device = 0;
     int num_cus = 256;
-    int fanout_variant = -1;        // EDGPU_FANOUT (A/B measurement); -1 = default kernel
+    int fanout_variant = -1;        // EDGPU_FANOUT=0|1 pins one of the two kernels; -1 = the tick's default
     uint64_t joined_rows = 0;       // sub-stream rows of the outputs added since the last tick
-    bool deframe_serial = false;    // EDGPU_DEFRAME_SERIAL (measurement): no deframe / fan-out overlap
     uint32_t tcp_walk = 2;          // EDGPU_TCP_WALK: 0 parallel chunk walk + resolve, 1 serial chain,
                                     // 2 segments of tcp_seg chunks (TcpParams.walk)
     uint32_t tcp_seg = 4;           // EDGPU_TCP_SEG
-    uint32_t ablate = 0;
     int timing = EDGPU_TIMING_ALL;  // edgpu_set_timing: which per-launch event pairs are recorded
-    uint32_t ingest_mode = 0;       // EDGPU_INGEST: 0 copy in k_ingest, 1 separate copy kernel
-    uint32_t tcp_copy = 3;          // EDGPU_INGEST_TCP: 3 frame state in SGPRs, DPP neighbour word, two
-                                    // frames per wave round; 2 the same with per-lane frame state;
-                                    // 1 one frame per round; 0 two loads per word
     hipStream_t stream = nullptr;
     // the RTSP-interleaved deframe (k_tcp_*) runs on `aux`: it reads only the call's TCP bytes
     // and writes deframe scratch, so it overlaps the previous tick's fan-out still on `stream`;
     // the host reads its report, then enqueues k_ingest (no cross-stream wait left on `stream`)
     hipStream_t aux = nullptr;
-    hipEvent_t ev_serial = nullptr;       // EDGPU_DEFRAME_SERIAL
     // the last keyframe index (it reads the segment tables the next deframe rewrites)
     hipEvent_t ev_kf = nullptr;
     bool kf_recorded = false;
@@ -382,7 +374,6 @@ struct edgpu_ctx {
     uint32_t* d_seg = nullptr;
     uint32_t* d_seg_sess = nullptr;
     uint8_t* d_blob = nullptr;
-    CopyJob* d_jobs = nullptr;
     // pinned-host ingest (EDGPU_PTR_PINNED): two device staging sets filled on `h2d`
     struct PinStage {
         edgpu_pkt_desc* desc = nullptr;
@@ -549,6 +540,7 @@ static int read_totals(edgpu_ctx* x, TickTotals* t);
 // host has not read the last tick's stats yet, whether a pass is owed is read from the device.
 static int owed_pass_known(edgpu_ctx* x, const char* what) {
     if (x->passes_more == -1 && x->fanout_launches) {
+        DEVICE_ENTER(x);
         TickTotals t;
         if (int r = read_totals(x, &t)) return r;
         x->passes_more = t.pass_next[x->pass_ord & 1u] != kNoPass ? 1 : 0;
@@ -627,7 +619,6 @@ int edgpu_ctx_create(const edgpu_config* cfg_in, edgpu_ctx** out) {
     if (dmalloc(&x->d_desc, sizeof(edgpu_pkt_desc) * (size_t)c.max_batch_packets) != hipSuccess) return bad("desc staging");
     if (dmalloc(&x->d_seg, sizeof(uint32_t) * ((size_t)c.max_batch_packets + 1)) != hipSuccess) return bad("seg staging");
     if (dmalloc(&x->d_seg_sess, sizeof(uint32_t) * (size_t)c.max_batch_packets) != hipSuccess) return bad("seg staging");
-    if (dmalloc(&x->d_jobs, sizeof(CopyJob) * (size_t)c.max_batch_packets) != hipSuccess) return bad("jobs");
     if (dmalloc(&x->d_arena, c.out_arena_bytes) != hipSuccess) return bad("fan-out arena");
     if (dmalloc(&x->d_out_desc, sizeof(edgpu_out_desc) * (size_t)c.max_out_packets) != hipSuccess) return bad("descriptors");
     if (dmalloc(&x->d_totals, sizeof(TickTotals)) != hipSuccess) return bad("totals");
@@ -644,13 +635,6 @@ int edgpu_ctx_create(const edgpu_config* cfg_in, edgpu_ctx** out) {
         if (hipMemcpy(x->d_totals, &t0, sizeof(t0), hipMemcpyHostToDevice) != hipSuccess) return bad("totals");
     }
     if (const char* v = getenv("EDGPU_FANOUT")) x->fanout_variant = atoi(v);
-#ifdef EDGPU_AB_VARIANTS                         // measurement builds only (edgpu_params.h)
-    if (const char* v = getenv("EDGPU_ABLATE")) x->ablate = (uint32_t)atoi(v);
-    if (const char* v = getenv("EDGPU_INGEST")) x->ingest_mode = (uint32_t)atoi(v) == 1 ? 1u : 0u;
-    if (const char* v = getenv("EDGPU_INGEST_TCP")) x->tcp_copy = (uint32_t)std::min(std::max(atoi(v), 0), 3);
-    // measurement: the deframe waits for everything enqueued before it (no overlap with the last fan-out)
-    if (const char* v = getenv("EDGPU_DEFRAME_SERIAL")) x->deframe_serial = atoi(v) != 0;
-#endif
     // the deframe walk (TcpParams.walk): "serial" / "parallel"
     if (const char* v = getenv("EDGPU_TCP_WALK"))
         x->tcp_walk = !strcmp(v, "serial") || !strcmp(v, "1") ? 1u : !strcmp(v, "seg") || !strcmp(v, "2") ? 2u : 0u;
@@ -691,7 +675,7 @@ int edgpu_ctx_destroy(edgpu_ctx* x) {
     if (x->d_tcp_tot) (void)hipFree(x->d_tcp_tot);
     if (x->d_tcp_raw) (void)hipFree(x->d_tcp_raw);
     if (x->d_img_status) (void)hipFree(x->d_img_status);
-    for (void* p : {(void*)x->d_desc, (void*)x->d_seg, (void*)x->d_seg_sess, (void*)x->d_jobs,
+    for (void* p : {(void*)x->d_desc, (void*)x->d_seg, (void*)x->d_seg_sess,
                     (void*)x->d_blob, (void*)x->d_arena, (void*)x->d_out_desc, (void*)x->d_totals, (void*)x->d_grow})
         if (p) (void)hipFree(p);
     for (auto& w : x->hist) for (auto& s : w) for (auto& e : s) if (e) (void)hipEventDestroy(e);
@@ -703,7 +687,6 @@ int edgpu_ctx_destroy(edgpu_ctx* x) {
     }
     if (x->h2d) (void)hipStreamDestroy(x->h2d);
     if (x->aux) (void)hipStreamSynchronize(x->aux);
-    if (x->ev_serial) (void)hipEventDestroy(x->ev_serial);
     if (x->ev_kf) (void)hipEventDestroy(x->ev_kf);
     if (x->aux) (void)hipStreamDestroy(x->aux);
     if (x->stream) (void)hipStreamDestroy(x->stream);
@@ -766,9 +749,8 @@ struct Readback {
     }
 };
 
-// The tick totals, after every stream of the context has drained.
+// The tick totals, after every stream of the context has drained (the caller has entered the device).
 static int read_totals(edgpu_ctx* x, TickTotals* t) {
-    DEVICE_ENTER(x);
     HIP_CHECK(sync_all(x));
     Readback rb(x);
     HIP_CHECK(rb.add(t, x->d_totals, sizeof(*t)));
@@ -1451,8 +1433,6 @@ int edgpu_subscriber_rewrite(edgpu_ctx* x, uint32_t handle, uint32_t track, cons
     if (track >= s.nsub / 2) return fail(EDGPU_BAD_ARGUMENT, "bad track");
     if (rw && (rw->flags & ~EDGPU_REWRITE_SSRC)) return fail(EDGPU_BAD_ARGUMENT, "bad rewrite flags");
     const bool on = rw && (rw->seq_delta || rw->ts_delta || (rw->flags & EDGPU_REWRITE_SSRC));
-    if (on && !fanout_rewrites(x->fanout_variant))
-        return fail(EDGPU_ERR, "the selected fan-out variant (EDGPU_FANOUT) has no rewrite stage");
     if (x->pending) return fail(EDGPU_ERR, "edgpu_keyframe_index must run after edgpu_ingest");
     DEVICE_ENTER(x);
     for (uint32_t k = 0; k < 2; k++) {
@@ -1684,7 +1664,7 @@ static int rebuild_index(edgpu_ctx* x) {
 // edgpu_keyframe_index.  With `tcp` (edgpu_ingest_interleaved) the deframe kernels have run
 // (`deframed`: on aux, observed by the host) or run first, inside the ingest timing events.
 static int enqueue_ingest(edgpu_ctx* x, const edgpu_pkt_desc* dd, uint32_t n, const uint32_t* ds, const uint32_t* dss,
-                          uint32_t nseg, const uint8_t* db, uint32_t copy_mode, bool host_src, const TcpParams* tcp = nullptr,
+                          uint32_t nseg, const uint8_t* db, bool host_src, const TcpParams* tcp = nullptr,
                           bool deframed = false) {
     IngestParams p;
     // a host batch: k_ingest records each packet's blob slot (edgpu_fanout_packet_info)
@@ -1694,7 +1674,7 @@ static int enqueue_ingest(edgpu_ctx* x, const edgpu_pkt_desc* dd, uint32_t n, co
     p.desc = dd; p.seg_off = ds; p.seg_sess = dss; p.blob = db;
     p.src_addr = tcp ? tcp->src_addr : nullptr;
     p.sessions = x->d_sessions.ptr; p.senders = x->d_senders.ptr; p.streams = x->d_streams.ptr;
-    p.jobs = x->d_jobs; p.npk = n; p.spec_min = x->cfg.ingest_spec_min; p.ablate = x->ablate; p.copy_mode = copy_mode; p.tcp_copy = x->tcp_copy;
+    p.npk = n; p.spec_min = x->cfg.ingest_spec_min;
     p.totals = x->d_totals;
     x->ing_slot ^= 1u;
     p.ing_slot = x->ing_slot;
@@ -1868,7 +1848,7 @@ int edgpu_ingest(edgpu_ctx* x, const edgpu_pkt_desc* desc, uint32_t n, const uin
         int k = 0;
         if ((r = stage_pinned(x, desc, n, seg_off, seg_sess, nseg, blob, blob_bytes, &k))) return r;
         const edgpu_ctx::PinStage& S = x->pin[k];
-        r = enqueue_ingest(x, S.desc, n, S.seg, S.sess, nseg, S.blob, x->ingest_mode, true);
+        r = enqueue_ingest(x, S.desc, n, S.seg, S.sess, nseg, S.blob, true);
         if (!r) x->pend_stage = k;
         else (void)hipEventRecord(S.consumed, x->stream);   // nothing will read the set: free it
         return r;
@@ -1891,7 +1871,7 @@ int edgpu_ingest(edgpu_ctx* x, const edgpu_pkt_desc* desc, uint32_t n, const uin
     } else if (where != EDGPU_PTR_DEVICE) {
         return fail(EDGPU_BAD_ARGUMENT, "bad pointer location");
     }
-    return enqueue_ingest(x, dd, n, ds, dss, nseg, db, x->ingest_mode, where == EDGPU_PTR_HOST);
+    return enqueue_ingest(x, dd, n, ds, dss, nseg, db, where == EDGPU_PTR_HOST);
 }
 
 int edgpu_ingest_interleaved(edgpu_ctx* x, const edgpu_tcp_read* reads, uint32_t n, const uint8_t* bytes,
@@ -1966,11 +1946,6 @@ int edgpu_ingest_interleaved(edgpu_ctx* x, const edgpu_tcp_read* reads, uint32_t
     // the deframe rewrites the segment tables the last keyframe index reads (a reserve above that
     // grew has synchronised `stream`); the fan-out after that index keeps running
     if (x->kf_recorded) HIP_CHECK(hipStreamWaitEvent(x->aux, x->ev_kf, 0));
-    if (x->deframe_serial) {
-        if (!x->ev_serial) HIP_CHECK(hipEventCreateWithFlags(&x->ev_serial, hipEventDisableTiming));
-        HIP_CHECK(hipEventRecord(x->ev_serial, x->stream));
-        HIP_CHECK(hipStreamWaitEvent(x->aux, x->ev_serial, 0));
-    }
     const uint8_t* raw = bytes;
     if (where == EDGPU_PTR_HOST) {
         if (!x->d_tcp_raw && dmalloc(&x->d_tcp_raw, x->cfg.max_batch_bytes) != hipSuccess)
@@ -2007,7 +1982,7 @@ int edgpu_ingest_interleaved(edgpu_ctx* x, const edgpu_tcp_read* reads, uint32_t
     HIP_CHECK(rb.add(results, x->d_tcp_results.ptr, n * sizeof(edgpu_tcp_result)));
     HIP_CHECK(rb.run());
     if (tot.status) return fail(EDGPU_OUT_OVERFLOW, "interleaved frames exceed max_batch_packets");
-    int r = enqueue_ingest(x, x->d_desc, 0, x->d_seg, x->d_seg_sess, ng, nullptr, 0, false, &p, true);
+    int r = enqueue_ingest(x, x->d_desc, 0, x->d_seg, x->d_seg_sess, ng, nullptr, false, &p, true);
     if (r) return r;
     for (const TcpGroup& G : groups) x->carry_len[G.session] = results[G.first_read + G.nreads - 1].carry;
     return EDGPU_OK;
@@ -2108,7 +2083,6 @@ static int launch_copy_pass(edgpu_ctx* x, edgpu_fanout_result* out) {
     f.arena_words = x->cfg.out_arena_bytes / 16;
     f.max_desc = x->cfg.max_out_packets;
     f.totals = x->d_totals;
-    f.ablate = x->ablate;
     hipStream_t cs = x->stream;
     HIP_CHECK(hist_mark(x, 0, 0, cs));
     HIP_CHECK(launch_fanout(f, x->tick_variant, x->num_cus, cs));
@@ -2162,12 +2136,7 @@ int edgpu_fanout_next(edgpu_ctx* x, edgpu_fanout_result* out, uint32_t* launched
     if (x->fanout_launches == 0) return fail(EDGPU_ERR, "no fan-out tick");
     DEVICE_ENTER(x);
     TickTotals t;
-    HIP_CHECK(sync_all(x));                  // the host has consumed the current pass
-    {
-        Readback rb(x);
-        HIP_CHECK(rb.add(&t, x->d_totals, sizeof(t)));
-        HIP_CHECK(rb.run());
-    }
+    if (int r = read_totals(x, &t)) return r;   // (its wait: the host has consumed the current pass)
     note_grow(x, t);
     if (t.status) {
         // a failed tick owes nothing: its remaining passes are dropped (the next fan-out counts
@@ -2200,12 +2169,7 @@ int edgpu_tick_stats_get(edgpu_ctx* x, edgpu_tick_stats* out) {
                                            "of a batch are set by its index)");
     DEVICE_ENTER(x);
     TickTotals t;
-    HIP_CHECK(sync_all(x));
-    {
-        Readback rb(x);
-        HIP_CHECK(rb.add(&t, x->d_totals, sizeof(t)));
-        HIP_CHECK(rb.run());
-    }
+    if (int r = read_totals(x, &t)) return r;
     note_grow(x, t);
     out->relayed_packets = t.relayed_packets;
     out->relayed_bytes = t.relayed_bytes;
@@ -2221,17 +2185,6 @@ int edgpu_tick_stats_get(edgpu_ctx* x, edgpu_tick_stats* out) {
     out->more_passes = (x->fanout_launches && t.pass_next[slot] != kNoPass) ? 1u : 0u;
     out->stream_errors = t.stream_errors;
     if (x->fanout_launches) x->passes_more = t.status ? 0 : (int)out->more_passes;
-#ifdef EDGPU_AB_VARIANTS
-    if (getenv("EDGPU_FAN_TAIL") && t.fan_done_max > t.fan_t0_min)   // 100-MHz s_memrealtime ticks
-        fprintf(stderr, "fan tail: span %.1f us, first exit at %.1f us, items %u; ingest span %.1f us, first exit at %.1f us\n",
-                (t.fan_done_max - t.fan_t0_min) / 100.0, (t.fan_done_min - t.fan_t0_min) / 100.0, t.nwork,
-                t.ing_last_span / 100.0, t.ing_last_first / 100.0);
-    if (getenv("EDGPU_FAN_TAIL") && t.ing_last_ph[0]) {
-        fprintf(stderr, "ingest phases (us per segment, %llu segments):", (unsigned long long)t.ing_last_ph[0]);
-        for (int k = 1; k < 7; k++) fprintf(stderr, " %.2f", t.ing_last_ph[k] / 100.0 / t.ing_last_ph[0]);
-        fprintf(stderr, "\n");
-    }
-#endif
     return EDGPU_OK;
 }
 
@@ -2247,12 +2200,7 @@ int edgpu_fanout_packet_info(edgpu_ctx* x, int64_t* arrivals, uint32_t* sources,
     if (kind != EDGPU_PTR_HOST && kind != EDGPU_PTR_DEVICE) return fail(EDGPU_BAD_ARGUMENT, "bad ptr_kind");
     DEVICE_ENTER(x);
     TickTotals t;
-    HIP_CHECK(sync_all(x));
-    {
-        Readback rb(x);
-        HIP_CHECK(rb.add(&t, x->d_totals, sizeof(t)));
-        HIP_CHECK(rb.run());
-    }
+    if (int r = read_totals(x, &t)) return r;
     if (t.status) return fail(t.status, "the last tick failed");
     const uint32_t npass = t.pass_desc[x->pass_ord & 1u];      // the current copy pass's descriptors
     if (n < npass) return fail(EDGPU_OUT_OVERFLOW, "array smaller than the pass's descriptors");
@@ -2323,12 +2271,7 @@ int edgpu_fanout_rows(edgpu_ctx* x, const uint32_t* sel, uint32_t nsel, edgpu_pa
     if (!nsel || !nrows) return EDGPU_OK;
     DEVICE_ENTER(x);
     TickTotals t;
-    HIP_CHECK(sync_all(x));
-    {
-        Readback rb(x);
-        HIP_CHECK(rb.add(&t, x->d_totals, sizeof(t)));
-        HIP_CHECK(rb.run());
-    }
+    if (int r = read_totals(x, &t)) return r;
     if (t.status) return fail(t.status, "the last tick failed");
     edgpu_packet_row* dr = rows;
     if (kind == EDGPU_PTR_HOST) { HIP_CHECK(x->d_rows.reserve(nrows, x->stream)); dr = x->d_rows.ptr; }
@@ -2374,12 +2317,7 @@ int edgpu_counters_get(edgpu_ctx* x, edgpu_counters* out) {
     if (!x || !out) return fail(EDGPU_BAD_ARGUMENT, "NULL argument");
     DEVICE_ENTER(x);
     TickTotals t;
-    HIP_CHECK(sync_all(x));
-    {
-        Readback rb(x);
-        HIP_CHECK(rb.add(&t, x->d_totals, sizeof(t)));
-        HIP_CHECK(rb.run());
-    }
+    if (int r = read_totals(x, &t)) return r;
     out->relayed_packets = t.cum_relayed_packets;
     out->relayed_bytes = t.cum_relayed_bytes;
     out->fanout_in_bytes = t.cum_fanout_in_bytes;

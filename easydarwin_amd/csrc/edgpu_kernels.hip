@@ -30,20 +30,9 @@ namespace edgpu {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-// k_ingest's slot-copy policy: bit 0 the copy's source loads non-temporal, bit 1 its ring stores
-// (so the copy's stream is the XCD L2's first victim and each packet's first line, read by the
-// header phase with the default policy, can still be there when the copy reads it again).
-#ifndef EDGPU_INGEST_NT
-#define EDGPU_INGEST_NT 0
-#endif
-__device__ __forceinline__ u32x4 ing_ld(const u32x4* p) {
-    if constexpr ((EDGPU_INGEST_NT & 1) != 0) return __builtin_nontemporal_load(p);
-    else return *p;
-}
-__device__ __forceinline__ void ing_st(u32x4* p, u32x4 v) {
-    if constexpr ((EDGPU_INGEST_NT & 2) != 0) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
+// k_ingest's slot-copy loads and ring stores (default cache policy)
+__device__ __forceinline__ u32x4 ing_ld(const u32x4* p) { return *p; }
+__device__ __forceinline__ void ing_st(u32x4* p, u32x4 v) { *p = v; }
 
 __device__ __forceinline__ uint32_t be16(const uint8_t* p) { return (uint32_t)p[0] << 8 | p[1]; }
 __device__ __forceinline__ uint32_t be32(const uint8_t* p) {
@@ -171,63 +160,6 @@ __device__ __forceinline__ T block_reduce(T v, T* scratch) {
 // Ingest
 // =========================================================================================
 
-// Slot copy of RTSP-interleaved frames inside the TCP byte stream (k_ingest, copy_mode 0).  The
-// frame's bytes [sp, lim) are misaligned by sh = sp & 15.  Each lane loads ONE aligned block
-// (blocks holding a byte of the frame only); slot word w is blocks w and w + 1 funnelled by sh,
-// and block w + 1 comes from the next lane by DPP (lane 63 takes the next round's lane 0 by
-// readlane).  A wave takes TD frames per round (EDGPU_INGEST_TCP=1 / 2: one / two)
-// and issues all their loads before its first store.  Four frames per round (162 VGPRs, 3 waves
-// per SIMD) measured slower: ingest incl. deframe 0.563 vs 0.435 ms (profiles/r02z21_*).
-template <uint32_t TD, int THREADS>
-__device__ __forceinline__ void tcp_slot_copy(uint32_t n, const uint32_t* p_slotb, const uint64_t* p_src,
-                                              const uint16_t* p_len, const uint8_t* p_snd, const uint64_t* p_vb,
-                                              const uint64_t* s_ring, const uint32_t* s_wmask) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    constexpr uint32_t kW = THREADS / 64;
-    auto lane0 = [](u32x4 v) {
-        return u32x4{(uint32_t)__builtin_amdgcn_readlane((int)v.x, 0), (uint32_t)__builtin_amdgcn_readlane((int)v.y, 0),
-                     (uint32_t)__builtin_amdgcn_readlane((int)v.z, 0), (uint32_t)__builtin_amdgcn_readlane((int)v.w, 0)};
-    };
-    for (uint32_t p = wid; p < n; p += TD * kW) {
-        u32x4 b[TD][4];
-        uint32_t sb[TD], fl[TD], sh[TD];
-#pragma unroll
-        for (uint32_t d = 0; d < TD; d++) {
-            const uint32_t pd = p + d * kW;
-            sb[d] = pd < n ? p_slotb[pd] : 0u;
-            const uint8_t* sp = reinterpret_cast<const uint8_t*>(sb[d] ? p_src[pd] : 0ull);
-            fl[d] = sb[d] ? 4u + p_len[pd] : 0u;                          // frame bytes
-            const uintptr_t a0 = (uintptr_t)sp & ~(uintptr_t)15;
-            sh[d] = (uint32_t)((uintptr_t)sp & 15);
-            const uint32_t nblk = sb[d] ? (uint32_t)(((uintptr_t)sp + fl[d] - 1 - a0) >> 4) + 1 : 0u;
-            const u32x4* ab = reinterpret_cast<const u32x4*>(a0);
-            const u32x4 z = u32x4{0u, 0u, 0u, 0u};
-            b[d][0] = (uint32_t)lane < nblk ? ab[lane] : z;
-            b[d][1] = (uint32_t)lane + 64 < nblk ? ab[lane + 64] : z;
-            b[d][2] = (uint32_t)lane + 128 < nblk ? ab[lane + 128] : z;
-            b[d][3] = lane == 0 && 192u < nblk ? ab[192] : z;           // lane 63 of round 2's neighbour
-        }
-#pragma unroll
-        for (uint32_t d = 0; d < TD; d++) {
-            if (sb[d] == 0) continue;                                    // uniform
-            const uint32_t pd = p + d * kW;
-            const uint32_t s = p_snd[pd];
-            u32x4* ring = reinterpret_cast<u32x4*>(s_ring[s]);
-            const uint64_t w0 = p_vb[pd] >> 4;
-            const uint32_t wm = s_wmask[s];
-            const uint32_t nw = sb[d] / 16;
-            u32x4 v0 = funnel16(b[d][0], wave_next(b[d][0], lane0(b[d][1])), sh[d]);
-            const u32x4 v1 = funnel16(b[d][1], wave_next(b[d][1], lane0(b[d][2])), sh[d]);
-            const u32x4 v2 = funnel16(b[d][2], wave_next(b[d][2], lane0(b[d][3])), sh[d]);
-            const int rem = (int)fl[d] - 16 * lane;                         // frame bytes from word `lane`
-            if (lane == 0) v0.x = slot_header(p_len[pd]);
-            if ((uint32_t)lane < nw) ring[(w0 + lane) & wm] = keep16(v0, rem);
-            if ((uint32_t)lane + 64 < nw) ring[(w0 + lane + 64) & wm] = keep16(v1, rem - 1024);
-            if ((uint32_t)lane + 128 < nw) ring[(w0 + lane + 128) & wm] = keep16(v2, rem - 2048);
-        }
-    }
-}
-
 // Lane l's 16 frame bytes at offset 4Q + r of (its aligned block `a`, lane l + 1's block);
 // lane 63 takes the next round's first block `last`.  The word offset Q is a template argument
 // (the caller branches on it once per frame: it is wave-uniform), so only the Q + 1 dwords that
@@ -272,12 +204,15 @@ __device__ __forceinline__ void tcp_frame_store(const u32x4 (&b)[3], u32x4 b3, u
     }
 }
 
-// tcp_slot_copy with the per-frame state in SGPRs: a frame's slot size, length and source
-// address are uniform across the wave (readfirstlane), and the one block past lane 63's second
-// round (block 192, needed by lane 63 of round 2 only) is a scalar load.  Fewer VGPRs per frame
-// in flight (12 instead of 16 + 3), so more frames per round fit the occupancy.  The stores go
-// through tcp_frame_store, specialised on the frame's word offset.
-// (EDGPU_INGEST_TCP=3: two frames per round, 4: four.)
+// Slot copy of RTSP-interleaved frames inside the TCP byte stream (k_ingest).  The frame's bytes
+// [sp, lim) are misaligned by sh = sp & 15.  Each lane loads ONE aligned block (blocks holding a
+// byte of the frame only); slot word w is blocks w and w + 1 funnelled by sh, and block w + 1
+// comes from the next lane by DPP (lane 63 takes the next round's lane 0 by readlane).  A wave
+// takes TD frames per round and issues all their loads before its first store.  The per-frame
+// state is in SGPRs: a frame's slot size, length and source address are uniform across the wave
+// (readfirstlane), and the one block past lane 63's second round (block 192, needed by lane 63 of
+// round 2 only) is a scalar load: 12 VGPRs per frame in flight, so four frames per round fit the
+// occupancy.  The stores go through tcp_frame_store, specialised on the frame's word offset.
 template <uint32_t TD, int THREADS>
 __device__ __forceinline__ void tcp_slot_copy_s(uint32_t n, const uint32_t* p_slotb, const uint64_t* p_src,
                                                 const uint16_t* p_len, const uint8_t* p_snd, const uint64_t* p_vb,
@@ -327,11 +262,9 @@ __device__ __forceinline__ void tcp_slot_copy_s(uint32_t n, const uint32_t* p_sl
     }
 }
 
-// DEPTH: packets per wave per slot-copy round; 4 by default (125 VGPRs, still 4 waves/SIMD),
-// EDGPU_INGEST_DEPTH=2 for A/B runs
-// THREADS: workgroup size, one packet per lane per round (256 by default; EDGPU_INGEST_THREADS=512
-// for A/B: one round for a C2 session's ~375 packets per tick)
-
+// One kIngestThreads-thread workgroup per session segment, one packet per lane per round; the slot
+// copy takes 4 packets per wave per round (125 VGPRs, still 4 waves/SIMD).
+//
 // SPEC (descriptor batches in the blob): the slot copy runs FIRST, at each packet's speculative
 // ring place -- every packet that passes the track / length test is taken to be enqueued with its
 // full length -- and the header words the reflector reads (packet bytes 0..27) are taken from the
@@ -340,10 +273,12 @@ __device__ __forceinline__ void tcp_slot_copy_s(uint32_t n, const uint32_t* p_sl
 // SSRC test refuses keeps its bytes as a hole in the ring (nothing points into it), a stripped
 // receive-time trailer stays as slack at its slot's end and its slot header is rewritten.  Ranks and
 // non-empty counts are scanned again only in a round where a decision differed from the guess.
-template <uint32_t DEPTH, int THREADS = kIngestThreads, bool SPEC = false>
+template <bool SPEC>
 // waves_per_eu(4): the kernel needs 4 waves per SIMD (4 resident 256-thread sessions per CU), and
 // the interleaved copy's four frames in flight fit 128 VGPRs that way
-__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) void k_ingest(IngestParams P) {
+__global__ __launch_bounds__(kIngestThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_ingest(IngestParams P) {
+    constexpr uint32_t DEPTH = 4;
+    constexpr int THREADS = kIngestThreads;
     constexpr int NW = THREADS / 64;
     const uint32_t seg = blockIdx.x;
     const int tid = threadIdx.x;
@@ -422,26 +357,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
     if (tid == 0) s_rtn = 0;
     if (tid < (int)S.ntracks) s_count[tid] = P.streams[S.first_stream + tid].packet_count;
     if (tid < (int)nsnd) c_lastacc[tid] = -1;
-#ifdef EDGPU_AB_VARIANTS
-    if (tid == 0) atomicMin(&P.totals->ing_t0_min, (unsigned long long)__builtin_amdgcn_s_memrealtime());
-    // measurement builds: thread 0's time per phase (s_memrealtime, 100 MHz), summed over the
-    // non-empty segments (EDGPU_FAN_TAIL prints the means): 1 session / sender state, 2 descriptor
-    // + header + SSRC filter, 3 rank scans, 4 meta stores + keyframe ballots, 5 slot copy, 6 tail
-    unsigned long long ph_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long ph_last = __builtin_amdgcn_s_memrealtime();
-#define EDGPU_ING_T(k)                                                                   \
-    do {                                                                                 \
-        if (tid == 0) {                                                                  \
-            const unsigned long long ph_now = __builtin_amdgcn_s_memrealtime();          \
-            ph_t[k] += ph_now - ph_last;                                                 \
-            ph_last = ph_now;                                                            \
-        }                                                                                \
-    } while (0)
-#else
-#define EDGPU_ING_T(k) do {} while (0)
-#endif
     __syncthreads();
-    EDGPU_ING_T(1);
 
     uint32_t in_pk = 0, in_bytes = 0;          // (a segment: < 2^21 packets, < 2^32 bytes)
     // ReflectorSession::fHasVideoKeyFrameUpdate before the chunk (every thread keeps the same)
@@ -557,22 +473,20 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
         auto rank_scan = [&](bool a, bool z, uint32_t sbytes) {
             const int lane = tid & 63, wid = tid >> 6;
             const uint64_t mx = (a ? 1ull | (uint64_t)(z ? 1 : 0) << 10 : 0ull) | (uint64_t)sbytes << 20;
-            const uint32_t ns = (EDGPU_ABL(P) & 64u) ? 0u : nsnd;
             uint64_t my_incl = 0, sib_incl = 0;
-            for (uint32_t s = 0; s < ns; s++) {                      // uniform
+            for (uint32_t s = 0; s < nsnd; s++) {                    // uniform
                 const uint64_t incl = wave_inclusive_scan_u64((a || sbytes) && ls == s ? mx : 0ull);
                 if (lane == 63) s_wsum[s][wid] = incl;
                 if (ls == s) my_incl = incl;
                 if ((ls ^ 1u) == s) sib_incl = incl;
             }
             __syncthreads();
-            EDGPU_ING_T(3);
-            if (tid < (int)ns) {
+            if (tid < (int)nsnd) {
                 uint64_t t = 0;
                 for (int w = 0; w < NW; w++) t += s_wsum[tid][w];
                 c_tot[tid] = t;
             }
-            if ((a || sbytes) && ns) {                               // (then ls < nsnd)
+            if ((a || sbytes) && nsnd) {                             // (then ls < nsnd)
                 uint64_t mb = 0, sb = 0;
                 for (int w = 0; w < wid; w++) { mb += s_wsum[ls][w]; sb += s_wsum[ls ^ 1u][w]; }
                 const uint64_t pre = mb + my_incl - mx;
@@ -581,7 +495,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
             }
         };
         // the slot copy of the round's packets with p_slotb > 0 from p_src to ring place p_vb (as
-        // copy_mode 0 below); with `capture`, lanes 0 and 1 leave slot words 0 and 1 for the header
+        // the header-first path's below); with `capture`, lanes 0 and 1 leave slot words 0 and 1 for the header
         auto slot_copy = [&](bool capture) {
             constexpr uint32_t kDepth = DEPTH, kW = THREADS / 64;
             const uint32_t lane = tid & 63, wid = tid >> 6;
@@ -692,7 +606,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
                 }
             }
             __syncthreads();
-            EDGPU_ING_T(2);
             len = p_len[tid];
         }
         // ---- receive-time trailer (ReflectorSocket::ProcessPacket, ReflectorStream.cpp:1960-1994):
@@ -801,7 +714,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
             p_vb[tid] = vb;
         }
         __syncthreads();
-        EDGPU_ING_T(4);
         // ---- keyframe index, part 2: a video key packet moves its sender's key pointer; an audio
         // packet anchors its sender's when the last key / audio event before it was a key packet
         // (none in the chunk before it: the session's flag); the newest such packet per sender wins
@@ -818,37 +730,12 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
             for (int w = 0; w < NW; w++)                              // the flag after the chunk
                 if (s_wev[w] & 1u) kflag = (s_wev[w] >> 1) & 1u;
         }
-        // ---- slot copy: here, one wave per packet (copy_mode 0), or as a job for
-        // k_ingest_copy's flat grid over packets (copy_mode 1) ----
-        if (SPEC || (EDGPU_ABL(P) & 32u)) {
-            // SPEC: copied above; or a timing ablation: no slot copy
-        } else if (EDGPU_COPY_MODE(P) == 0 && P.src_addr && EDGPU_TCP_COPY(P) >= 1) {   // frames inside the TCP byte stream
-            if (EDGPU_TCP_COPY(P) == 3) tcp_slot_copy_s<kTcpFramesPerRound, THREADS>(n, p_slotb, p_src, p_len, p_snd, p_vb, s_ring, s_wmask);
-            else if (EDGPU_TCP_COPY(P) >= 2) tcp_slot_copy<2, THREADS>(n, p_slotb, p_src, p_len, p_snd, p_vb, s_ring, s_wmask);
-            else tcp_slot_copy<1, THREADS>(n, p_slotb, p_src, p_len, p_snd, p_vb, s_ring, s_wmask);
-        } else if (EDGPU_COPY_MODE(P) == 0 && P.src_addr) {   // same, two aligned loads per word (A/B)
-            const int lane = tid & 63, wid = tid >> 6;
-            for (uint32_t p = wid; p < n; p += THREADS / 64) {
-                const uint32_t sb = p_slotb[p];
-                if (sb == 0) continue;
-                const uint32_t s = p_snd[p];
-                const uint8_t* sp = reinterpret_cast<const uint8_t*>(p_src[p]);
-                u32x4* ring = reinterpret_cast<u32x4*>(s_ring[s]);
-                const uint64_t w0 = p_vb[p] >> 4;
-                const uint32_t wm = s_wmask[s];
-                const uint8_t* lim = sp + 4 + p_len[p];
-                // all of a lane's (<= 3) words are loaded before its first store, as below
-                const uint32_t nw = sb / 16;
-                const u32x4 z = u32x4{0u, 0u, 0u, 0u};
-                u32x4 v0 = lane < nw ? load16_unaligned(sp + 16 * lane, lim) : z;
-                const u32x4 v1 = lane + 64 < nw ? load16_unaligned(sp + 16 * (lane + 64), lim) : z;
-                const u32x4 v2 = lane + 128 < nw ? load16_unaligned(sp + 16 * (lane + 128), lim) : z;
-                if (lane == 0) v0.x = slot_header(p_len[p]);
-                if (lane < nw) ring[(w0 + lane) & wm] = v0;
-                if (lane + 64 < nw) ring[(w0 + lane + 64) & wm] = v1;
-                if (lane + 128 < nw) ring[(w0 + lane + 128) & wm] = v2;
-            }
-        } else if (EDGPU_COPY_MODE(P) == 0) {
+        // ---- slot copy: one wave per packet ----
+        if (SPEC) {
+            // copied above
+        } else if (P.src_addr) {   // frames inside the TCP byte stream
+            tcp_slot_copy_s<kTcpFramesPerRound, THREADS>(n, p_slotb, p_src, p_len, p_snd, p_vb, s_ring, s_wmask);
+        } else {
             // kDepth packets per wave per round, and a slot is at most 129 words (2060 + 4 B),
             // so every lane issues all of its loads (<= 3 x 16 B per packet) before its first
             // store: a wave keeps kDepth whole slots in flight instead of waiting out one load
@@ -882,15 +769,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
                         if (lane + 64 * k < nw[d]) ing_st(ring + ((w0 + lane + 64 * k) & wm), v[d][k]);
                 }
             }
-        } else if (valid) {
-            CopyJob j;
-            j.ring = acc ? s_ring[ls] : 0ull;
-            j.vword = vb >> 4;
-            j.wmask = acc ? s_wmask[ls] : 0u;
-            j.src_slot = slot;
-            j.len = slotb ? len : 0u;
-            j.sender = S.first_sender + ls;
-            P.jobs[i] = j;
         }
         // ---- advance per-sender / per-stream state ----
         if (tid < (int)nsnd) {
@@ -904,7 +782,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
         if (tid < (int)S.ntracks) s_count[tid] += (c_tot[2 * tid] & 1023) + (c_tot[2 * tid + 1] & 1023);
         if (tid < (int)nsnd) c_lastacc[tid] = -1;
         __syncthreads();
-        EDGPU_ING_T(5);
     }
 
     if (tid < (int)nsnd) {
@@ -935,55 +812,14 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
     if (tid == 0) {
         for (int w = 0; w < NW; w++) { t1 += scan64[w] & ((1ull << 21) - 1); t2 += scan64[w] >> 21; }
     }
-    if (tid == 0 && !(EDGPU_ABL(P) & 16u)) {
+    if (tid == 0) {
         atomicAdd(&P.totals->cum_ingested_packets, (unsigned long long)t1);
         atomicAdd(&P.totals->cum_ingested_bytes, (unsigned long long)t2);
         atomicAdd(&P.totals->ing_pk[P.ing_slot], (unsigned long long)t1);
         atomicAdd(&P.totals->ing_b[P.ing_slot], (unsigned long long)t2);
     }
     if (seg == 0 && tid == 0) { P.totals->ing_pk[P.ing_slot ^ 1u] = 0; P.totals->ing_b[P.ing_slot ^ 1u] = 0; }
-#ifdef EDGPU_AB_VARIANTS
-    EDGPU_ING_T(6);
-    if (tid == 0 && e > b) {
-        for (int k = 1; k < 7; k++) atomicAdd(&P.totals->ing_ph[k], ph_t[k]);
-        atomicAdd(&P.totals->ing_ph[0], 1ull);
-    }
-    if (tid == 0) {
-        const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-        atomicMin(&P.totals->ing_done_min, t);
-        atomicMax(&P.totals->ing_done_max, t);
-    }
-#endif
 }
-
-// =========================================================================================
-// Slot copy, blob -> byte rings.  Each group of kCopyLanes lanes copies one packet's slot as
-// 16-B words, rewriting word 0's 4-byte prefix to the '$' 0 BE16(len) frame header.  A flat
-// grid over packets keeps every CU busy regardless of how packets spread over sessions.
-// =========================================================================================
-#ifdef EDGPU_AB_VARIANTS
-constexpr int kCopyThreads = 256, kCopyLanes = 16;
-
-__global__ __launch_bounds__(kCopyThreads) void k_ingest_copy(IngestParams P) {
-    const uint32_t g = blockIdx.x * (kCopyThreads / kCopyLanes) + threadIdx.x / kCopyLanes;
-    const uint32_t lane = threadIdx.x % kCopyLanes;
-    if (g >= P.npk) return;
-    const CopyJob j = P.jobs[g];
-    if (j.len == 0) return;
-    const uint32_t nw = (j.len + 4 + 15) >> 4;
-    // words a later packet of the same batch laps are left to it (k_ingest has already
-    // advanced vbyte_end), so a batch larger than the ring stays deterministic
-    const uint64_t vend = P.senders[j.sender].vbyte_end >> 4, cap = (uint64_t)j.wmask + 1;
-    const uint64_t live = vend > cap ? vend - cap : 0ull;
-    const u32x4* src = reinterpret_cast<const u32x4*>(P.blob + (uint64_t)j.src_slot * 16);
-    u32x4* ring = reinterpret_cast<u32x4*>(j.ring);
-    for (uint32_t k = lane; k < nw; k += kCopyLanes) {
-        u32x4 v = src[k];
-        if (k == 0) v.x = slot_header(j.len);
-        if (j.vword + k >= live) ring[(j.vword + k) & j.wmask] = v;
-    }
-}
-#endif  // EDGPU_AB_VARIANTS
 
 // =========================================================================================
 // Keyframe index + audio anchor: one wave per session segment.
@@ -1052,13 +888,6 @@ __device__ uint64_t wave_first_arrival_at(const SenderDev& D, const PktMeta* met
 __device__ __forceinline__ void reset_tick_totals(TickTotals* t) {
     t->relayed_packets = 0; t->relayed_bytes = 0; t->arena_bytes = 0;   // the ingest counters stay
     t->status = 0; t->nwork = 0; t->fan_next = 0; t->stream_errors = 0;
-    t->fan_t0_min = ~0ull; t->fan_done_min = ~0ull; t->fan_done_max = 0;
-#ifdef EDGPU_AB_VARIANTS
-    // measurement builds: the last ingest's span and first workgroup exit, then a reset
-    t->ing_last_span = t->ing_done_max - t->ing_t0_min; t->ing_last_first = t->ing_done_min - t->ing_t0_min;
-    t->ing_t0_min = ~0ull; t->ing_done_min = ~0ull; t->ing_done_max = 0;
-    for (int k = 0; k < 8; k++) { t->ing_last_ph[k] = t->ing_ph[k]; t->ing_ph[k] = 0; }
-#endif
     // a pass the previous tick still owed is lost now (its host never called edgpu_fanout_next)
     if (t->pass_next[t->pass_slot & 1u] != kNoPass) t->cum_lost_passes++;
     t->pass_slot = 0;
@@ -1529,193 +1358,20 @@ __global__ void k_blocked(BlockedParams P) {
 // =========================================================================================
 
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) {
-    return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v);
-}
 
 // -----------------------------------------------------------------------------------------
-// k_fanout3: LDS-staged, line-aligned write-many.  The chunk is loaded from HBM into LDS once;
-// for every sub-stream each lane then reads the word that lands on its lane of a 128-B-
-// aligned destination window (the realignment is a per-sub-stream shift of the LDS read
-// index), so every 1 KiB wave store covers whole cache lines.  A 16-B misaligned
-// destination costs ~30 % of write bandwidth on MI355X (tools/store_peak2.hip), and the
-// sub-streams' pieces start at arbitrary 16-B offsets.  TCP channel bytes are patched in
-// registers before the single store.
-// -----------------------------------------------------------------------------------------
-template <int THREADS, int CHUNK>
-constexpr int fanout3_lds() {
-    return CHUNK * 129 * 16 + (CHUNK + 2) * 8 + CHUNK * 16 + ((((CHUNK * 129 + 31) / 32) + 3) & ~3) * 4 +
-           (THREADS < 256 ? THREADS : 256) * 36 + (THREADS / 64) * 8;
-}
-
-template <int THREADS, int CHUNK>
-__global__ __attribute__((amdgpu_flat_work_group_size(1, THREADS)))
-void k_fanout3(FanoutParams P) {
-    constexpr int CWORDS = CHUNK * 129;
-    constexpr int NW = (CWORDS + 7 + THREADS - 1) / THREADS;
-    constexpr int NWAVES = THREADS / 64;
-    constexpr int QB = THREADS < 256 ? THREADS : 256;                  // sub-streams per LDS batch
-    const uint32_t nwork = P.totals->nwork;
-    if (P.totals->status == EDGPU_OUT_OVERFLOW) return;
-    const int tid = threadIdx.x;
-    // All LDS is one dynamic region carved at 16-B-aligned offsets (Guideline 17: no static
-    // __shared__ in front of it), so the ds_read_b128 of the chunk words stay aligned.
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    constexpr int SM = ((CWORDS + 31) / 32 + 3) & ~3;                  // startmap words, x4
-    u32x4* cbuf = reinterpret_cast<u32x4*>(lds);                       // CWORDS words
-    uint64_t* m_vb = reinterpret_cast<uint64_t*>(cbuf + CWORDS);       // CHUNK + 2
-    uint32_t* m_id = reinterpret_cast<uint32_t*>(m_vb + CHUNK + 2);    // CHUNK (multiple of 4)
-    uint32_t* m_len = m_id + CHUNK;
-    uint32_t* m_vc = m_len + CHUNK;
-    uint32_t* m_nzp = m_vc + CHUNK;                                    // CHUNK: ordinal -> packet
-    uint32_t* startmap = m_nzp + CHUNK;                                // SM
-    int64_t* q_dw0 = reinterpret_cast<int64_t*>(startmap + SM);        // QB
-    int64_t* q_off = q_dw0 + QB;
-    uint32_t* q_fw = reinterpret_cast<uint32_t*>(q_off + QB);
-    uint32_t* q_ch = q_fw + QB;
-    uint32_t* q_db = q_ch + QB;
-    uint32_t* q_p0 = q_db + QB;
-    uint32_t* q_hl = q_p0 + QB;
-    unsigned long long* s_red = reinterpret_cast<unsigned long long*>(q_hl + QB);   // NWAVES
-    unsigned long long wire = 0, inb = 0;
-    u32x4* out = reinterpret_cast<u32x4*>(P.arena);
-
-    for (uint32_t w = blockIdx.x; w < nwork; w += gridDim.x) {
-        const FanWork it = P.work[w];
-        const SenderDev& D = P.senders[it.sender];
-        const uint64_t lo = it.lo;
-        const uint64_t head = D.head;
-        const uint32_t np = (uint32_t)min((uint64_t)CHUNK, head - lo);
-        const PktMeta* meta = reinterpret_cast<const PktMeta*>(D.meta);
-        if (tid < (int)np) {
-            const PktMeta m = meta[(lo + tid) & D.pk_mask];
-            m_vb[tid] = m.vbyte; m_id[tid] = (uint32_t)m.id; m_len[tid] = m.len; m_vc[tid] = m.vcount;
-            inb += m.len;
-        }
-        if (tid == (int)np) m_vb[np] = (lo + np == head) ? D.vbyte_end : meta[(lo + np) & D.pk_mask].vbyte;
-        for (int k = tid; k < (int)((CWORDS + 31) / 32); k += THREADS) startmap[k] = 0;
-        __syncthreads();
-        const uint64_t vb0 = m_vb[0];
-        const uint32_t nw = uni((uint32_t)((m_vb[np] - vb0) >> 4));
-        if (tid < (int)np && m_len[tid] != 0) {
-            const uint32_t sw = (uint32_t)((m_vb[tid] - vb0) >> 4);
-            atomicOr(&startmap[sw >> 5], 1u << (sw & 31));
-            m_nzp[m_vc[tid] - m_vc[0]] = tid;              // non-empty ordinal -> packet
-        }
-        // chunk HBM -> LDS (buffer loads, one 32-bit offset per lane; wrap handled per word)
-        {
-            const uint32_t wmask = uni(D.word_mask);
-            const uint32_t rstart = uni((uint32_t)((vb0 >> 4) & wmask));
-            const bool wraps = rstart + nw > wmask + 1;
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                reinterpret_cast<u32x4*>(D.ring) + (wraps ? 0u : rstart), 0,
-                wraps ? (wmask + 1) * 16 : nw * 16, 0x00020000);
-#pragma unroll
-            for (int j = 0; j < (CWORDS + THREADS - 1) / THREADS; j++) {
-                const uint32_t wi = tid + j * THREADS;
-                if (wi < nw)
-                    cbuf[wi] = __builtin_amdgcn_raw_buffer_load_b128(
-                        rs, (wraps ? ((rstart + wi) & wmask) : wi) * 16u, 0, 0);
-            }
-        }
-        const uint32_t qb = P.sub_range[2 * it.sender], qe = P.sub_range[2 * it.sender + 1];
-        for (uint32_t q0 = qb; q0 < qe; q0 += QB) {
-            const uint32_t nq = min((uint32_t)QB, qe - q0);
-            if (tid < (int)nq) {
-                const SubDev& Q = P.subs[P.sub_index[q0 + tid]];
-                uint32_t fw = 0xFFFFFFFFu, p0 = 0xFFFFFFFFu;
-                if (Q.nonempty && Q.a < lo + np) {
-                    const uint64_t first = Q.a > lo ? Q.a : lo;
-                    p0 = (uint32_t)(first - lo);
-                    fw = (uint32_t)((m_vb[p0] - vb0) >> 4);
-                }
-                q_fw[tid] = fw;
-                q_p0[tid] = p0;
-                q_dw0[tid] = (int64_t)(Q.out_base >> 4) + ((int64_t)(vb0 - Q.vstart) >> 4);
-                q_off[tid] = (int64_t)(Q.out_base - Q.vstart) + (Q.transport ? 0 : 4);
-                q_ch[tid] = Q.transport ? ((uint32_t)Q.channel << 8) : 0u;
-                q_db[tid] = Q.desc_base - Q.vcstart;
-                q_hl[tid] = Q.transport ? 4u : 0u;
-            }
-            __syncthreads();
-            for (uint32_t q = 0; q < nq && !(EDGPU_ABL(P) & 2u); q++) {
-                const uint32_t fw = uni(q_fw[q]);
-                if (fw >= nw) continue;
-                const int64_t A = (int64_t)uni64((uint64_t)q_dw0[q]) + fw;     // first dest word
-                const uint32_t s = (uint32_t)(A & 7);                          // words past a 128-B line
-                // descriptor from the exact first word; lanes below it get a wrapped (huge)
-                // offset and are dropped by the range check, as are lanes past the chunk
-                const __amdgpu_buffer_rsrc_t os = __builtin_amdgcn_make_buffer_rsrc(
-                    out + A, 0, (nw - fw) * 16, 0x00020000);
-                const uint32_t chbits = uni(q_ch[q]);
-#pragma unroll
-                for (int j = 0; j < NW; j++) {
-                    const uint32_t lane_w = tid + j * THREADS;               // word in the aligned window
-                    const uint32_t src = fw + lane_w - s;                    // chunk word it carries
-                    const uint32_t srcc = src < (uint32_t)CWORDS ? src : 0u;
-                    u32x4 v = cbuf[srcc];
-                    if (chbits && ((startmap[srcc >> 5] >> (srcc & 31)) & 1u)) v.x |= chbits;
-                    __builtin_amdgcn_raw_buffer_store_b128(v, os, (lane_w - s) * 16u, 0, 0);
-                }
-            }
-            // descriptors: one wave per sub-stream, lanes mapped onto a 128-B-aligned window of
-            // the sub-stream's descriptor array (8 descriptors per line)
-            {
-                const int lane = tid & 63, wv = tid >> 6;
-                // non-empty packets of this chunk: ordinals [0, nzc)
-                const uint32_t nzc = (uint32_t)__builtin_amdgcn_readfirstlane(
-                    (int)(np ? m_vc[np - 1] - m_vc[0] + (m_len[np - 1] != 0) : 0));
-                for (uint32_t q = wv; q < (EDGPU_ABL(P) & 1u ? 0u : nq); q += NWAVES) {
-                    const uint32_t p0 = q_p0[q];
-                    if (p0 >= np) continue;
-                    const uint32_t o0 = m_vc[p0] - m_vc[0];                   // first ordinal
-                    if (o0 >= nzc) continue;
-                    const uint32_t d0 = q_db[q] + m_vc[p0];                   // its descriptor
-                    const uint32_t sh = d0 & 7;
-                    const uint32_t o = o0 + lane - sh;                        // ordinal of this lane
-                    if (lane >= (int)sh && o < nzc) {
-                        const uint32_t p = m_nzp[o];
-                        const uint32_t len = m_len[p];
-                        const uint64_t off = (uint64_t)(q_off[q] + (int64_t)m_vb[p]);
-                        const uint32_t wlen = len + q_hl[q];
-                        u32x4 dv;
-                        dv.x = (uint32_t)off; dv.y = (uint32_t)(off >> 32); dv.z = wlen; dv.w = m_id[p];
-                        if (d0 - sh + lane < P.max_desc) reinterpret_cast<u32x4*>(P.desc)[d0 - sh + lane] = dv;
-                        wire += wlen;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    unsigned long long a = wire, b = inb;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o, 64); b += __shfl_down(b, o, 64); }
-    if ((tid & 63) == 0) s_red[tid >> 6] = a;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long tot = 0;
-        for (int i = 0; i < NWAVES; i++) tot += s_red[i];
-        if (tot) { atomicAdd(&P.totals->relayed_bytes, tot); atomicAdd(&P.totals->cum_relayed_bytes, tot); }
-    }
-    __syncthreads();
-    if ((tid & 63) == 0) s_red[tid >> 6] = b;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long tot = 0;
-        for (int i = 0; i < NWAVES; i++) tot += s_red[i];
-        if (tot) atomicAdd(&P.totals->cum_fanout_in_bytes, tot);
-    }
-}
-
-// -----------------------------------------------------------------------------------------
-// k_fanout4: k_fanout3's line-aligned LDS write-many, restructured so that loading a chunk never
-// stalls the store stream.
+// k_fanout4: LDS-staged, line-aligned write-many.  A work item's chunk is loaded from HBM into
+// LDS once; for every sub-stream each lane then reads the word that lands on its lane of a 128-B-
+// aligned destination window (the realignment is a per-sub-stream shift of the LDS read index),
+// so every 1 KiB wave store covers whole cache lines.  A 16-B misaligned destination costs ~30 %
+// of write bandwidth on MI355X, and the sub-streams' pieces start at arbitrary 16-B offsets.  The
+// per-output patch (TCP channel byte, rewrite) is made in registers before the single store.
+// Loading a chunk never stalls the store stream:
 //   * Everything a work item needs before its loads comes from one 64-B FanWork record
 //     (k_plan_final), read through the constant address space, so it lands in SGPRs: the
 //     ring's buffer resource is scalar and the chunk's 16-B loads issue back to back.
-//     (k_fanout3 built that resource from a per-lane load, which the compiler lowers to a
-//     waterfall loop that waits for every load in turn.)
+//     (Built from a per-lane load, the compiler lowers that resource to a waterfall loop that
+//     waits for every load in turn.)
 //   * Sub-stream parameters are one 48-B FanSub per sub-stream in sender order, also scalar
 //     loads: no sub_index -> SubDev chain and no per-sender LDS batch.
 //   * The NEXT item's chunk words and packet metadata are loaded into registers as soon as
@@ -1723,8 +1379,8 @@ void k_fanout3(FanoutParams P) {
 //     the LDS image is refilled from those registers after the end-of-item barrier.
 //   * The slot-start bitmap (TCP channel patch) is double-buffered by item parity, so
 //     clearing it needs no extra barrier.
-// Stores: per sub-stream, lanes walk the destination in whole 128-B lines (k_fanout3), with a
-// uniform trip count, so no store instruction is issued for words past the chunk.
+// Stores: per sub-stream, lanes walk the destination in whole 128-B lines, with a uniform trip
+// count, so no store instruction is issued for words past the chunk.
 // -----------------------------------------------------------------------------------------
 // Loads a record written by an earlier kernel through the constant address space: uniform
 // addresses become scalar (s_load) loads, whose results live in SGPRs.
@@ -1740,14 +1396,8 @@ __device__ __forceinline__ T const_load(const T* p) {
     return v;
 }
 
-// The per-output patch of one 16-B arena word (word `w` of the chunk's LDS image `cb`, slot
-// starts marked in bitmap `sm`): the RTSP-interleaved channel byte (RTSPSessionInterface.cpp:
-// 329-336) and the rewrite stage (kRw*).  A slot's first word holds the 4-B '$' 0 BE16(len)
-// header and packet bytes 0..11: RTP seq (bytes 2-3), timestamp (4-7) and SSRC (8-11), or an
-// RTCP packet's sender SSRC (4-7); an SR's RTP timestamp (packet bytes 16-19) is in the second
-// word.  Fields past the packet's length are left alone; CSRC lists and extensions are never
-// touched.
-// The patched form of a slot's first word (computed for every lane, selected by `start`).
+// The patched form of a slot's first word (computed for every lane, selected by `start`): see
+// fan_patch.
 __device__ __forceinline__ u32x4 fan_patch_start(u32x4 v, const FanSub& f, bool start) {
     u32x4 p = v;
     if (f.ch & 1u) p.x |= f.ch & 0xFF00u;
@@ -1785,55 +1435,14 @@ __device__ __forceinline__ u32x4 fan_patch(u32x4 v, const FanSub& f, uint32_t w,
     return fan_patch_start(v, f, start);
 }
 
-// fan_patch with the slot-start test as a divergent branch: the patch arithmetic runs only on
-// lanes that hold a slot's first word (and only in waves that have one), in place, with no
-// per-dword selects.  Same result as fan_patch.
-__device__ __forceinline__ u32x4 fan_patch_branchy(u32x4 v, const FanSub& f, uint32_t w, const uint32_t* sm,
-                                                   const u32x4* cb) {
-    const bool start = (sm[w >> 5] >> (w & 31)) & 1u;
-    if ((f.rw & kRwRtcp) && !start && w > 0 && ((sm[(w - 1) >> 5] >> ((w - 1) & 31)) & 1u)) {   // RTCP only: rare
-        const u32x4 h = cb[w - 1];
-        const uint32_t hl = ((h.x >> 8) & 0xFF00u) | (h.x >> 24);
-        if (hl >= 20 && ((h.y >> 8) & 0xFFu) == 200u) v.y = __builtin_bswap32(__builtin_bswap32(v.y) + f.rw_ts);
-    }
-    if (start) {
-        if (f.ch & 1u) v.x |= f.ch & 0xFF00u;
-        if (f.rw) {
-            const uint32_t len = ((v.x >> 8) & 0xFF00u) | (v.x >> 24);
-            if (!(f.rw & kRwRtcp)) {
-                if (len >= 12) {
-                    const uint32_t seq = (((v.y >> 8) & 0xFF00u) | (v.y >> 24)) + (f.rw >> 16);
-                    v.y = (v.y & 0xFFFFu) | ((seq >> 8) & 0xFFu) << 16 | (seq & 0xFFu) << 24;
-                    v.z = __builtin_bswap32(__builtin_bswap32(v.z) + f.rw_ts);
-                    if (f.rw & kRwSsrc) v.w = f.rw_ssrc_be;
-                }
-            } else if ((f.rw & kRwSsrc) && len >= 8) {
-                v.z = f.rw_ssrc_be;
-            }
-        }
-    }
-    return v;
-}
-
-// Bits [c0, c0 + 64) of a slot-start bitmap of `nw32` words as one wave-uniform mask (bit l =
-// word c0 + l; words before 0 or past the bitmap read as 0).  Every lane reads the same three
-// LDS words (a broadcast), so the per-word test becomes a shift of an SGPR pair.
-__device__ __forceinline__ uint64_t row_mask(const uint32_t* sm, int c0, int nw32) {
-    const int b = c0 >> 5, sh = c0 & 31;
-    auto word = [&](int i) -> uint64_t { return (i >= 0 && i < nw32) ? (uint64_t)sm[i] : 0ull; };
-    const uint64_t lo = word(b) | word(b + 1) << 32, hi = word(b + 2);
-    return (lo >> sh) | (sh ? hi << (64 - sh) : 0ull);
-}
-
-// LFS: FanSub records staged in LDS per work item (up to kLfs), so the store loop's per-window
-// record read is an LDS broadcast instead of a scalar load that can miss the scalar cache
-constexpr int kLfs = 64;
-template <int THREADS, int CHUNK, int LFS = 0>
+template <int THREADS, int CHUNK>
 constexpr int fanout4_lds() {
     return CHUNK * kSlotWordsMax * 16 + (CHUNK + 2) * 8 + 4 * CHUNK * 4 +
-           2 * ((((CHUNK * kSlotWordsMax + 31) / 32) + 3) & ~3) * 4 + (THREADS / 64) * 8 +
-           (LFS ? kLfs * (int)sizeof(FanSub) : 0);
+           2 * ((((CHUNK * kSlotWordsMax + 31) / 32) + 3) & ~3) * 4 + (THREADS / 64) * 8;
 }
+
+// cache policy of the arena stores (raw_buffer_store aux): non-temporal
+constexpr int kAuxNt = 2;
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
@@ -1843,9 +1452,8 @@ typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
 // only when the LDS image is written, so the registers stay exactly as loaded while the loads
 // are in flight.  All are buffer loads (vector-memory counter only; a flat load would also hold
 // the LDS counter that the store loop waits on).
-template <int THREADS, int NL, int LAUX = 0>
-__device__ __forceinline__ void fan4_issue(const FanWork& it, int tid, u32x4 (&r)[NL], u32x3& ma, u32x2& mb,
-                                           bool skip_words = false) {
+template <int THREADS, int NL>
+__device__ __forceinline__ void fan4_issue(const FanWork& it, int tid, u32x4 (&r)[NL], u32x3& ma, u32x2& mb) {
     const uint32_t wmask = it.wmask, nw = it.nw;
     const uint32_t rstart = (uint32_t)(it.vb0 >> 4) & wmask;
     const bool wraps = rstart + nw > wmask + 1;
@@ -1854,9 +1462,9 @@ __device__ __forceinline__ void fan4_issue(const FanWork& it, int tid, u32x4 (&r
 #pragma unroll
     for (int j = 0; j < NL; j++) {
         const uint32_t wi = tid + j * THREADS;
-        if ((uint32_t)(j * THREADS) < nw && !skip_words)   // uniform: no load past the chunk's lines
+        if ((uint32_t)(j * THREADS) < nw)                  // uniform: no load past the chunk's lines
             r[j] = __builtin_amdgcn_raw_buffer_load_b128(
-                rs, wraps ? (wi < nw ? ((rstart + wi) & wmask) * 16u : 0xFFFFFFFFu) : wi * 16u, 0, LAUX);
+                rs, wraps ? (wi < nw ? ((rstart + wi) & wmask) * 16u : 0xFFFFFFFFu) : wi * 16u, 0, 0);
     }
     const __amdgpu_buffer_rsrc_t ms = __builtin_amdgcn_make_buffer_rsrc(
         reinterpret_cast<void*>(it.meta), 0, (it.pkmask + 1) * (uint32_t)sizeof(PktMeta), 0x00020000);
@@ -1865,24 +1473,10 @@ __device__ __forceinline__ void fan4_issue(const FanWork& it, int tid, u32x4 (&r
     mb = __builtin_amdgcn_raw_buffer_load_b64(ms, mo + 24u, 0, 0);
 }
 
-// AUX: cache policy of the arena stores (0 plain; A/B variants: 2 nt, 16 sc1, 17 sc0 sc1);
-// DNT: non-temporal descriptor stores; LAUX: cache policy of the chunk loads.
-// SU: store-loop unroll (SU LDS reads in flight before the SU stores of a sub-stream window;
-// needs the VGPRs of 1 workgroup per CU at 1024 threads)
-// WPE: minimum waves per SIMD the register allocation must allow (8 = two 1024-thread
-// workgroups per CU, i.e. <= 64 VGPRs); 0 leaves it to the compiler.
-// PM: how the store loop finds slot starts for the per-output patch: 0 one bitmap bit per lane
-// (LDS read per word), 1 one wave-uniform 64-bit mask per wave row (row_mask).
-// DYN: work items claimed from a tick-global counter (one atomic per item, two items ahead of
-// use) instead of a static stride over blockIdx, so unequal items cannot leave a long tail.
-// PACE (A/B of store issue rate): 1 every window takes the patch path (an identity window then
-// pays the rewrite's bitmap read per word); 2 s_sleep after every store row.
-// HW: the two halves of the workgroup write two sub-streams' windows at once (each half walks
-// its window with THREADS/2 lanes), so one window's record / offset chain overlaps the other's
-// stores.
-template <int THREADS, int CHUNK, int AUX = 0, int DNT = 0, int LAUX = 0, int SU = 1, int WPE = 0, int PM = 0,
-          int LFS = 0, int DYN = 0, int PACE = 0, int HW = 0>
-__global__ __attribute__((amdgpu_flat_work_group_size(1, THREADS), amdgpu_waves_per_eu(WPE ? WPE : 1)))
+// Work items are claimed from a tick-global counter (one atomic per item, two items ahead of
+// use), so unequal items cannot leave a long tail; the arena stores are non-temporal.
+template <int THREADS, int CHUNK>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, THREADS), amdgpu_waves_per_eu(1)))
 void k_fanout4(FanoutParams P) {
     constexpr int CWORDS = CHUNK * kSlotWordsMax;
     constexpr int NL = (CWORDS + THREADS - 1) / THREADS;              // chunk words per lane
@@ -1903,24 +1497,6 @@ void k_fanout4(FanoutParams P) {
     uint32_t* m_nzp = m_vc + CHUNK;                                    // non-empty ordinal -> packet
     uint32_t* smap = m_nzp + CHUNK;                                    // 2 x SM, by item parity
     unsigned long long* s_red = reinterpret_cast<unsigned long long*>(smap + 2 * SM);
-    uint32_t* s_fs = reinterpret_cast<uint32_t*>(s_red + NWAVES);       // LFS: kLfs FanSub records
-    constexpr uint32_t kFsw = sizeof(FanSub) / 4;                      // dwords per record
-    static_assert(!LFS || kLfs * kFsw <= (uint32_t)THREADS, "one staged dword per lane");
-    // the item's FanSub q as SGPRs: from the LDS copy (LFS) or a scalar load
-    auto fansub = [&](const FanWork& w, uint32_t q) -> FanSub {
-        if constexpr (LFS) {
-            if (q - w.qb < (uint32_t)kLfs) {
-                FanSub f;
-                uint32_t* d = reinterpret_cast<uint32_t*>(&f);
-                const uint32_t* src = s_fs + (q - w.qb) * kFsw;
-#pragma unroll
-                for (uint32_t i = 0; i < kFsw; i++) d[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)src[i]);
-                return f;
-            }
-        }
-        return const_load(P.fansub + q);
-    };
-    uint32_t fsw = 0;                                                  // LFS: this lane's staged dword
     u32x4* out = reinterpret_cast<u32x4*>(P.arena);
     unsigned long long wire = 0, inb = 0;
 
@@ -1928,28 +1504,21 @@ void k_fanout4(FanoutParams P) {
     u32x4 r[NL];
     u32x3 ma;
     u32x2 mb;
-    // DYN: s_claim[par] holds the item claimed for use two items later (written by thread 0
-    // after an image barrier, read by everyone after the next one)
+    // s_claim[par] holds the item claimed for use two items later (written by thread 0 after an
+    // image barrier, read by everyone after the next one)
     __shared__ uint32_t s_claim[2];
-    uint32_t w = blockIdx.x;
-    if constexpr (DYN) {
-        if (tid == 0) {
-            s_claim[0] = atomicAdd(&P.totals->fan_next, 1u);
-            s_claim[1] = atomicAdd(&P.totals->fan_next, 1u);
-        }
-        __syncthreads();
-        w = s_claim[0];
+    if (tid == 0) {
+        s_claim[0] = atomicAdd(&P.totals->fan_next, 1u);
+        s_claim[1] = atomicAdd(&P.totals->fan_next, 1u);
     }
+    __syncthreads();
+    uint32_t w = s_claim[0];
     FanWork nx;
     if (w < nwork) {
         nx = const_load(P.work + w);
-        fan4_issue<THREADS, NL, LAUX>(nx, tid, r, ma, mb, (EDGPU_ABL(P) & 4u) != 0);
-        if constexpr (LFS) {
-            const uint32_t nq = min(nx.qe - nx.qb, (uint32_t)kLfs);
-            if ((uint32_t)tid < nq * kFsw) fsw = reinterpret_cast<const uint32_t*>(P.fansub + nx.qb)[tid];
-        }
+        fan4_issue<THREADS, NL>(nx, tid, r, ma, mb);
     }
-    uint32_t wnext = DYN ? s_claim[1] : 0u;      // DYN: the item to prefetch during this one
+    uint32_t wnext = s_claim[1];                 // the item to prefetch during this one
     uint32_t wpref = 0;                          // the item whose loads are in flight
     for (uint32_t par = 0; w < nwork; w = wpref, par ^= 1u) {
         const FanWork it = nx;
@@ -1974,33 +1543,20 @@ void k_fanout4(FanoutParams P) {
             }
         }
         if (tid == 0) m_vb[np] = vb0 + (uint64_t)nw * 16;
-        if constexpr (LFS) {
-            if ((uint32_t)tid < min(it.qe - it.qb, (uint32_t)kLfs) * kFsw) s_fs[tid] = fsw;
-        }
         __syncthreads();
         // ---- the other parity's bitmap is free now: clear it for the next item ----------
         for (int k = tid; k < SM; k += THREADS) smap[(par ^ 1u) * SM + k] = 0;
         // ---- next item's loads, in flight under this item's stores ------------------------
-        uint32_t wn = w + gridDim.x;
-        if constexpr (DYN) {
-            wn = wnext;                                            // claimed one item ago
-            if (tid == 0) s_claim[par] = atomicAdd(&P.totals->fan_next, 1u);   // for the item after it
-        }
+        const uint32_t wn = wnext;                                         // claimed one item ago
+        if (tid == 0) s_claim[par] = atomicAdd(&P.totals->fan_next, 1u);   // for the item after it
         wpref = wn;
         if (wn < nwork) {
             nx = const_load(P.work + wn);
-            fan4_issue<THREADS, NL, LAUX>(nx, tid, r, ma, mb, (EDGPU_ABL(P) & 4u) != 0);
-            if constexpr (LFS) {
-                const uint32_t nq = min(nx.qe - nx.qb, (uint32_t)kLfs);
-                if ((uint32_t)tid < nq * kFsw) fsw = reinterpret_cast<const uint32_t*>(P.fansub + nx.qb)[tid];
-            }
+            fan4_issue<THREADS, NL>(nx, tid, r, ma, mb);
         }
         // ---- write the chunk to every sub-stream of the sender ----------------------------
-        constexpr uint32_t WT = HW ? THREADS / 2 : THREADS;                    // lanes per window
-        const uint32_t wtid = HW ? (uint32_t)tid % WT : (uint32_t)tid;
-        const uint32_t q0 = HW ? uni((uint32_t)tid / WT) : 0u;
-        for (uint32_t q = it.qb + q0; q < it.qe && !(EDGPU_ABL(P) & 2u); q += HW ? 2u : 1u) {
-            const FanSub f = fansub(it, q);
+        for (uint32_t q = it.qb; q < it.qe; q++) {
+            const FanSub f = const_load(P.fansub + q);
             if (f.a >= lo + np) continue;
             const uint32_t p0 = f.a > lo ? (uint32_t)(f.a - lo) : 0u;
             const uint32_t fw = uni((uint32_t)((m_vb[p0] - vb0) >> 4));
@@ -2008,39 +1564,21 @@ void k_fanout4(FanoutParams P) {
             if (A < 0 || (uint64_t)A + (nw - fw) > P.arena_words) { set_status(&P.totals->status, EDGPU_OUT_OVERFLOW); continue; }
             const uint32_t s = (uint32_t)(A & 7);                              // words past a line
             const __amdgpu_buffer_rsrc_t os = __builtin_amdgcn_make_buffer_rsrc(out + A, 0, (nw - fw) * 16, 0x00020000);
-            const bool patch = PACE == 1 || (f.ch & 1u) || f.rw;               // uniform
-            const uint32_t nj = (nw - fw + s + WT - 1) / WT;
-            for (uint32_t j = 0; j < nj; j += SU) {
-                u32x4 v[SU];
-                uint32_t srcc[SU];
-#pragma unroll
-                for (int k = 0; k < SU; k++) {
-                    const uint32_t src = fw + wtid + (j + k) * WT - s;         // chunk word of the lane's
-                    srcc[k] = src < (uint32_t)CWORDS ? src : 0u;               // word of the aligned window
-                    if (k == 0 || j + k < nj) v[k] = cbuf[srcc[k]];            // uniform guard
-                }
-#pragma unroll
-                for (int k = 0; k < SU; k++) {
-                    if (k > 0 && j + k >= nj) break;
-                    if (patch) {
-                        if (PM == 0 || (f.rw & kRwRtcp)) {
-                            v[k] = fan_patch(v[k], f, srcc[k], sm, cbuf);
-                        } else {
-                            const int c0 = (int)(fw + (j + k) * WT + (wtid & ~63u)) - (int)s;
-                            const uint64_t m = uni64(row_mask(sm, c0, SM));
-                            if (m) v[k] = fan_patch_start(v[k], f, (m >> lane) & 1u);
-                        }
-                    }
-                    __builtin_amdgcn_raw_buffer_store_b128(v[k], os, (wtid + (j + k) * WT - s) * 16u, 0, AUX);
-                }
-                if constexpr (PACE == 2) __builtin_amdgcn_s_sleep(1);
+            const bool patch = (f.ch & 1u) || f.rw;                            // uniform
+            const uint32_t nj = (nw - fw + s + THREADS - 1) / THREADS;
+            for (uint32_t j = 0; j < nj; j++) {
+                const uint32_t src = fw + tid + j * THREADS - s;               // chunk word of the lane's
+                const uint32_t srcc = src < (uint32_t)CWORDS ? src : 0u;       // word of the aligned window
+                u32x4 v = cbuf[srcc];
+                if (patch) v = fan_patch(v, f, srcc, sm, cbuf);
+                __builtin_amdgcn_raw_buffer_store_b128(v, os, (tid + j * THREADS - s) * 16u, 0, kAuxNt);
             }
         }
         // ---- descriptors: one wave per sub-stream, a 128-B-aligned window of its array ----
         {
             const uint32_t nzc = np ? m_vc[np - 1] - vc0 + (m_len[np - 1] != 0) : 0u;
-            for (uint32_t q = it.qb + wv; q < it.qe && !(EDGPU_ABL(P) & 1u); q += NWAVES) {
-                const FanSub f = fansub(it, q);
+            for (uint32_t q = it.qb + wv; q < it.qe; q += NWAVES) {
+                const FanSub f = const_load(P.fansub + q);
                 if (f.a >= lo + np) continue;
                 const uint32_t p0 = f.a > lo ? (uint32_t)(f.a - lo) : 0u;
                 const uint32_t o0 = m_vc[p0] - vc0;                            // first ordinal
@@ -2055,16 +1593,13 @@ void k_fanout4(FanoutParams P) {
                     const uint32_t wlen = len + ((f.ch & 1u) ? 4u : 0u);
                     u32x4 dv;
                     dv.x = (uint32_t)off; dv.y = (uint32_t)(off >> 32); dv.z = wlen; dv.w = m_id[p];
-                    if (d0 - sh + lane < P.max_desc) {
-                        if constexpr (DNT) __builtin_nontemporal_store(dv, reinterpret_cast<u32x4*>(P.desc) + d0 - sh + lane);
-                        else reinterpret_cast<u32x4*>(P.desc)[d0 - sh + lane] = dv;
-                    }
+                    if (d0 - sh + lane < P.max_desc) reinterpret_cast<u32x4*>(P.desc)[d0 - sh + lane] = dv;
                     wire += wlen;
                 }
             }
         }
         __syncthreads();
-        if constexpr (DYN) wnext = s_claim[par];                  // visible after the barrier
+        wnext = s_claim[par];                                     // visible after the barrier
     }
     unsigned long long a = wire, b = inb;
 #pragma unroll
@@ -2110,15 +1645,7 @@ struct Fan6 {
 template <int THREADS, int CHUNK>
 constexpr int fanout6_lds() { return Fan6<THREADS, CHUNK>::lds(); }
 
-// PP: the per-output patch as per-packet fix-ups.  The rows store every word that is not a
-// packet's first word (nor, for an RTCP rewrite, its second); then one wave writes those words,
-// patched, one lane per packet of the window.  The words are disjoint, so no ordering is
-// needed, and the patch arithmetic runs once per packet instead of on every stored word.
-// PF: each sub-stream window's FanSub record is loaded one window ahead (while the previous
-// window's rows are stored), instead of in up to three dependent scalar-load round trips at the
-// window's start.
-// BP: the patch as a divergent branch on the slot-start test (fan_patch_branchy).
-template <int THREADS, int CHUNK, int AUX = 2, int PP = 0, int PF = 0, int BP = 0>
+template <int THREADS, int CHUNK>
 __global__ __attribute__((amdgpu_flat_work_group_size(1, THREADS))) void k_fanout6(FanoutParams P) {
     using F = Fan6<THREADS, CHUNK>;
     constexpr int CWORDS = F::CWORDS, NL = F::NL, NWAVES = F::NWAVES, SM = F::SM;
@@ -2173,9 +1700,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, THREADS))) void k_fanou
 
     for (int k = tid; k < 3 * SM; k += THREADS) smb[k] = 0;
     if (tid == 0) { s_claim[0] = atomicAdd(&P.totals->fan_next, 1u); s_claim[1] = atomicAdd(&P.totals->fan_next, 1u); }
-#ifdef EDGPU_AB_VARIANTS
-    if (tid == 0) atomicMin(&P.totals->fan_t0_min, (unsigned long long)__builtin_amdgcn_s_memrealtime());
-#endif
     __syncthreads();
     uint32_t w = s_claim[0], wnext = s_claim[1];
     FanWork cur, nx;
@@ -2197,11 +1721,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, THREADS))) void k_fanou
         const uint64_t lo = it.lo, vb0 = it.vb0;
         const uint32_t np = it.np, nw = it.nw, vc0 = it.vc0;
         // ---- write the chunk to every sub-stream of the sender ----------------------------
-        FanSub fnext;
-        bool have_next = false;                                            // PF: fnext is record q
-        for (uint32_t q = it.qb; q < it.qe && !(EDGPU_ABL(P) & 2u); q++) {
-            const FanSub f = (PF && have_next) ? fnext : const_load(P.fansub + q);
-            have_next = false;
+        for (uint32_t q = it.qb; q < it.qe; q++) {
+            const FanSub f = const_load(P.fansub + q);
             if (f.a >= lo + np) continue;
             const uint32_t p0 = f.a > lo ? (uint32_t)(f.a - lo) : 0u;
             const uint32_t fw = uni((uint32_t)((m.vb[p0] - vb0) >> 4));
@@ -2211,46 +1732,18 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, THREADS))) void k_fanou
             const __amdgpu_buffer_rsrc_t os = __builtin_amdgcn_make_buffer_rsrc(out + A, 0, (nw - fw) * 16, 0x00020000);
             const bool patch = (f.ch & 1u) || f.rw;                            // uniform
             const uint32_t nj = (nw - fw + s + THREADS - 1) / THREADS;
-            if (PF && q + 1 < it.qe) { fnext = const_load(P.fansub + q + 1); have_next = true; }
-            if (PP && patch) {
-                const bool second = (f.rw & kRwRtcp) != 0;                     // the SR timestamp word too
-                for (uint32_t j = 0; j < nj; j++) {
-                    const uint32_t src = fw + tid + j * THREADS - s;
-                    const uint32_t srcc = src < (uint32_t)CWORDS ? src : 0u;
-                    const u32x4 v = m.cb[srcc];
-                    bool skip = (sm[srcc >> 5] >> (srcc & 31)) & 1u;
-                    if (second && srcc > 0) skip |= (sm[(srcc - 1) >> 5] >> ((srcc - 1) & 31)) & 1u;
-                    if (!skip) __builtin_amdgcn_raw_buffer_store_b128(v, os, (tid + j * THREADS - s) * 16u, 0, AUX);
-                }
-                if (wv == (q - it.qb) % NWAVES) {                              // one wave: the packets
-                    const uint32_t p = p0 + lane;
-                    const uint32_t len = p < np ? m.len[p] : 0u;
-                    if (len != 0) {
-                        const uint32_t st = (uint32_t)((m.vb[p] - vb0) >> 4);  // the slot's first word
-                        const u32x4 h = m.cb[st];
-                        __builtin_amdgcn_raw_buffer_store_b128(fan_patch_start(h, f, true), os, (st - fw) * 16u, 0, AUX);
-                        if (second && len >= 13) {                             // a second word in the slot
-                            u32x4 v1 = m.cb[st + 1];
-                            if (len >= 20 && ((h.y >> 8) & 0xFFu) == 200u)     // an SR: its RTP timestamp
-                                v1.y = __builtin_bswap32(__builtin_bswap32(v1.y) + f.rw_ts);
-                            __builtin_amdgcn_raw_buffer_store_b128(v1, os, (st + 1 - fw) * 16u, 0, AUX);
-                        }
-                    }
-                }
-                continue;
-            }
             for (uint32_t j = 0; j < nj; j++) {
                 const uint32_t src = fw + tid + j * THREADS - s;               // chunk word of the lane's
                 const uint32_t srcc = src < (uint32_t)CWORDS ? src : 0u;       // word of the aligned window
                 u32x4 v = m.cb[srcc];
-                if (patch) v = BP ? fan_patch_branchy(v, f, srcc, sm, m.cb) : fan_patch(v, f, srcc, sm, m.cb);
-                __builtin_amdgcn_raw_buffer_store_b128(v, os, (tid + j * THREADS - s) * 16u, 0, AUX);
+                if (patch) v = fan_patch(v, f, srcc, sm, m.cb);
+                __builtin_amdgcn_raw_buffer_store_b128(v, os, (tid + j * THREADS - s) * 16u, 0, kAuxNt);
             }
         }
         // ---- descriptors: one wave per sub-stream, a 128-B-aligned window of its array ----
         {
             const uint32_t nzc = np ? m.vc[np - 1] - vc0 + (m.len[np - 1] != 0) : 0u;
-            for (uint32_t q = it.qb + wv; q < it.qe && !(EDGPU_ABL(P) & 1u); q += NWAVES) {
+            for (uint32_t q = it.qb + wv; q < it.qe; q += NWAVES) {
                 const FanSub f = const_load(P.fansub + q);
                 if (f.a >= lo + np) continue;
                 const uint32_t p0 = f.a > lo ? (uint32_t)(f.a - lo) : 0u;
@@ -2306,208 +1799,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, THREADS))) void k_fanou
     if (tid == 0) {
         unsigned long long tot = 0;
         for (int k = 0; k < NWAVES; k++) tot += s_red[k];
-        if (tot) atomicAdd(&P.totals->cum_fanout_in_bytes, tot);
-    }
-#ifdef EDGPU_AB_VARIANTS
-    if (tid == 0) {
-        const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-        atomicMin(&P.totals->fan_done_min, t);
-        atomicMax(&P.totals->fan_done_max, t);
-    }
-#endif
-}
-
-// -----------------------------------------------------------------------------------------
-// k_fanout5: the write-many at low wave count with asynchronous chunk staging.  Measured on
-// the box (tools/store_peak3.hip): the same line-aligned window stores reach ~5.8 TB/s with 4
-// waves per CU and no load phases, against ~5.3 TB/s at 32 waves per CU with load phases
-// between chunks.  So each CU runs few waves, and the next chunk (slot words and packet
-// metadata) is staged by LDS-DMA (global_load_lds_dwordx4, no VGPRs) into the other half of a
-// double-buffered LDS image while the current chunk is written out.  Barriers are raw
-// s_barrier with explicit counter waits, so the DMA stays in flight across them; the one
-// vmcnt(0) per item (which also retires that item's stores) is where the next image lands.
-// -----------------------------------------------------------------------------------------
-template <int THREADS, int CHUNK>
-struct Fan5 {
-    static constexpr int CWORDS = CHUNK * kSlotWordsMax;
-    static constexpr int NLD = (CWORDS + THREADS - 1) / THREADS;       // DMA words per lane
-    static constexpr int CBUF = NLD * THREADS;                         // words per image
-    static constexpr int SM = ((CWORDS + 31) / 32 + 3) & ~3;
-    static constexpr int NWAVES = THREADS / 64;
-    // per buffer: chunk words, 2 metadata words per packet; then bitmaps, ordinals, reduction
-    static constexpr int lds() {
-        return 2 * CBUF * 16 + 2 * 2 * CHUNK * 16 + 2 * SM * 4 + 2 * CHUNK * 4 + NWAVES * 8;
-    }
-};
-
-template <int THREADS, int CHUNK>
-constexpr int fanout5_lds() { return Fan5<THREADS, CHUNK>::lds(); }
-
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-// One global_load_lds_dwordx4: 16 B per lane from `g` into LDS at M0 + 16 * lane.  Issued from
-// inline asm so the compiler's counter pass does not see an LDS write in flight (it would
-// otherwise wait for the DMA before every later LDS access, serialising the pipeline); the
-// kernel waits for it explicitly (vmcnt(0) at the top of the next item).
-__device__ __forceinline__ void glds16(const void* g, uint32_t lds_base) {
-    uint32_t keep;                                     // M0 is reserved: save and restore it
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(g), "s"(lds_base) : "memory");
-}
-__device__ __forceinline__ uint32_t lds_addr(void* p) { return uni((uint32_t)(size_t)(lptr_t)p); }
-
-// LDS-DMA of one work item into image `img` / metadata `mimg` (both wave-linear: lane l of a
-// wave-instruction lands at base + 16 l).  Lanes past the chunk re-read a valid word.
-template <int THREADS, int CHUNK>
-__device__ __forceinline__ void fan5_stage(const FanWork& it, int tid, u32x4* img, u32x4* mimg) {
-    using F = Fan5<THREADS, CHUNK>;
-    const uint32_t wmask = it.wmask, nw = it.nw;
-    const uint32_t r0 = (uint32_t)(it.vb0 >> 4);
-    const u32x4* ring = reinterpret_cast<const u32x4*>(it.ring);
-    const uint32_t wbase = uni((uint32_t)tid & ~63u);
-    const uint32_t ibase = lds_addr(img) + wbase * 16u;
-#pragma unroll
-    for (int j = 0; j < F::NLD; j++) {
-        if ((uint32_t)(j * THREADS) < nw) {                    // uniform
-            const uint32_t wi = j * THREADS + tid;
-            const uint32_t src = (r0 + min(wi, nw - 1)) & wmask;
-            glds16(ring + src, ibase + (uint32_t)(j * THREADS) * 16u);
-        }
-    }
-    if (tid < 2 * CHUNK && it.np) {      // metadata: 2 words per packet; exec-masked lanes write nothing
-        const uint32_t p = min((uint32_t)tid >> 1, it.np - 1);
-        const u32x4* meta = reinterpret_cast<const u32x4*>(it.meta);
-        const uint64_t e = (it.lo + p) & it.pkmask;
-        glds16(meta + 2 * e + (tid & 1), lds_addr(mimg) + wbase * 16u);
-    }
-}
-
-template <int THREADS, int CHUNK, int AUX = 0>
-__global__ __attribute__((amdgpu_flat_work_group_size(1, THREADS)))
-void k_fanout5(FanoutParams P) {
-    using F = Fan5<THREADS, CHUNK>;
-    constexpr int CWORDS = F::CWORDS, SM = F::SM, NWAVES = F::NWAVES;
-    static_assert(CHUNK <= 56 && 2 * CHUNK <= THREADS, "");
-    const uint32_t nwork = uni(P.totals->nwork);
-    if (uni((uint32_t)P.totals->status) == (uint32_t)EDGPU_OUT_OVERFLOW) return;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const uint32_t wv = uni((uint32_t)tid >> 6);
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    u32x4* cimg = reinterpret_cast<u32x4*>(lds);                       // 2 x CBUF words
-    u32x4* mimg = cimg + 2 * F::CBUF;                                  // 2 x 2*CHUNK words
-    uint32_t* smap = reinterpret_cast<uint32_t*>(mimg + 4 * CHUNK);    // 2 x SM
-    uint32_t* nzp = smap + 2 * SM;                                     // 2 x CHUNK
-    unsigned long long* s_red = reinterpret_cast<unsigned long long*>(nzp + 2 * CHUNK);
-    u32x4* out = reinterpret_cast<u32x4*>(P.arena);
-    unsigned long long wire = 0, inb = 0;
-
-    for (int k = tid; k < 2 * SM; k += THREADS) smap[k] = 0;
-    uint32_t w = blockIdx.x;
-    FanWork cur, nxt;
-    if (w < nwork) {
-        cur = const_load(P.work + w);
-        fan5_stage<THREADS, CHUNK>(cur, tid, cimg, mimg);
-    }
-    if (w + gridDim.x < nwork) nxt = const_load(P.work + w + gridDim.x);
-    for (uint32_t b = 0; w < nwork; w += gridDim.x, b ^= 1u) {
-        const uint64_t lo = cur.lo, vb0 = cur.vb0;
-        const uint32_t np = cur.np, nw = cur.nw, vc0 = cur.vc0;
-        u32x4* cb = cimg + b * F::CBUF;
-        const u32x4* mb = mimg + b * 2 * CHUNK;
-        uint32_t* sm = smap + b * SM;
-        uint32_t* nz = nzp + b * CHUNK;
-        // this item's image has landed (this also retires the previous item's stores), and
-        // every wave is past the previous item: the other buffer is free
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        const uint32_t wn = w + gridDim.x;
-        if (wn < nwork) fan5_stage<THREADS, CHUNK>(nxt, tid, cimg + (b ^ 1u) * F::CBUF, mimg + (b ^ 1u) * 2 * CHUNK);
-        // slot-start bitmap and non-empty ordinals of this item; clear the other bitmap
-        for (int k = tid; k < SM; k += THREADS) smap[(b ^ 1u) * SM + k] = 0;
-        if ((uint32_t)tid < np) {
-            const u32x4 m0 = mb[2 * tid], m1 = mb[2 * tid + 1];
-            const uint64_t vbyte = (uint64_t)m0.y << 32 | m0.x;
-            inb += m1.z & 0xFFFFu;                                     // len:16 | seq:16
-            if ((m1.z & 0xFFFFu) != 0) {
-                const uint32_t sw = (uint32_t)((vbyte - vb0) >> 4);
-                atomicOr(&sm[sw >> 5], 1u << (sw & 31));
-                nz[m1.w - vc0] = tid;
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        const FanWork it = cur;
-        cur = nxt;
-        if (wn + gridDim.x < nwork) nxt = const_load(P.work + wn + gridDim.x);
-        // ---- write the chunk to every sub-stream of the sender (k_fanout3's line-aligned
-        // windows, uniform trip count) ----
-        for (uint32_t q = it.qb; q < it.qe && !(EDGPU_ABL(P) & 2u); q++) {
-            const FanSub f = const_load(P.fansub + q);
-            if (f.a >= lo + np) continue;
-            const uint32_t p0 = f.a > lo ? (uint32_t)(f.a - lo) : 0u;
-            const u32x4 mp = mb[2 * p0];
-            const uint32_t fw = uni((uint32_t)((((uint64_t)mp.y << 32 | mp.x) - vb0) >> 4));
-            const int64_t A = f.dw + (int64_t)(vb0 >> 4) + fw;
-            if (A < 0 || (uint64_t)A + (nw - fw) > P.arena_words) { set_status(&P.totals->status, EDGPU_OUT_OVERFLOW); continue; }
-            const uint32_t s = (uint32_t)(A & 7);
-            const __amdgpu_buffer_rsrc_t os = __builtin_amdgcn_make_buffer_rsrc(out + A, 0, (nw - fw) * 16, 0x00020000);
-            const bool patch = (f.ch & 1u) || f.rw;                            // uniform
-            const uint32_t nj = (nw - fw + s + THREADS - 1) / THREADS;
-            for (uint32_t j = 0; j < nj; j++) {
-                const uint32_t lw = tid + j * THREADS;
-                const uint32_t src = fw + lw - s;
-                const uint32_t srcc = src < (uint32_t)CWORDS ? src : 0u;
-                u32x4 v = cb[srcc];
-                if (patch) v = fan_patch(v, f, srcc, sm, cb);
-                __builtin_amdgcn_raw_buffer_store_b128(v, os, (lw - s) * 16u, 0, AUX);
-            }
-        }
-        // ---- descriptors: one wave per sub-stream, 128-B-aligned windows ----
-        {
-            const u32x4 ml = mb[2 * (np - 1) + 1];
-            const uint32_t nzc = np ? ml.w - vc0 + ((ml.z & 0xFFFFu) != 0) : 0u;
-            for (uint32_t q = it.qb + wv; q < it.qe && !(EDGPU_ABL(P) & 1u); q += NWAVES) {
-                const FanSub f = const_load(P.fansub + q);
-                if (f.a >= lo + np) continue;
-                const uint32_t p0 = f.a > lo ? (uint32_t)(f.a - lo) : 0u;
-                const uint32_t vcp0 = mb[2 * p0 + 1].w;
-                const uint32_t o0 = vcp0 - vc0;
-                if (o0 >= nzc) continue;
-                const uint32_t d0 = f.db + vcp0;
-                const uint32_t sh = d0 & 7;
-                const uint32_t o = o0 + lane - sh;
-                if ((uint32_t)lane >= sh && o < nzc) {
-                    const uint32_t p = nz[o];
-                    const u32x4 m0 = mb[2 * p], m1 = mb[2 * p + 1];
-                    const uint64_t off = (uint64_t)(f.off + (int64_t)((uint64_t)m0.y << 32 | m0.x));
-                    const uint32_t wlen = (m1.z & 0xFFFFu) + ((f.ch & 1u) ? 4u : 0u);
-                    u32x4 dv;
-                    dv.x = (uint32_t)off; dv.y = (uint32_t)(off >> 32); dv.z = wlen; dv.w = m0.z;
-                    if (d0 - sh + lane < P.max_desc) reinterpret_cast<u32x4*>(P.desc)[d0 - sh + lane] = dv;
-                    wire += wlen;
-                }
-            }
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    unsigned long long a = wire, bb = inb;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o, 64); bb += __shfl_down(bb, o, 64); }
-    if (lane == 0) s_red[tid >> 6] = a;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long tot = 0;
-        for (int i = 0; i < NWAVES; i++) tot += s_red[i];
-        if (tot) { atomicAdd(&P.totals->relayed_bytes, tot); atomicAdd(&P.totals->cum_relayed_bytes, tot); }
-    }
-    __syncthreads();
-    if (lane == 0) s_red[tid >> 6] = bb;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long tot = 0;
-        for (int i = 0; i < NWAVES; i++) tot += s_red[i];
         if (tot) atomicAdd(&P.totals->cum_fanout_in_bytes, tot);
     }
 }
@@ -2897,22 +2188,9 @@ hipError_t launch_ingest(const IngestParams& p, uint32_t nseg, hipStream_t st) {
     }
     // descriptor batches in the blob take the speculative copy (k_ingest SPEC); frames inside a
     // TCP byte stream find their lengths in their own first bytes and keep the header-first order
-    const bool spec = !p.tcp_groups && !p.src_addr && EDGPU_COPY_MODE(p) == 0 && p.spec_min && p.npk >= (uint64_t)p.spec_min * nseg;
-#ifdef EDGPU_AB_VARIANTS   // measurement builds: the ingest shapes of Appendix A.2
-    static const int depth = [] { const char* v = getenv("EDGPU_INGEST_DEPTH"); return v ? atoi(v) : 4; }();
-    static const int threads = [] { const char* v = getenv("EDGPU_INGEST_THREADS"); return v && atoi(v) == 512 ? 512 : 256; }();
-    if (threads == 512) EDGPU_LAUNCH((k_ingest<4, 512>), dim3(nseg), dim3(512), 0, st, p);
-    else if (depth == 2) EDGPU_LAUNCH(k_ingest<2>, dim3(nseg), dim3(kIngestThreads), 0, st, p);
-    else if (spec && !getenv("EDGPU_INGEST_NOSPEC")) EDGPU_LAUNCH((k_ingest<4, kIngestThreads, true>), dim3(nseg), dim3(kIngestThreads), 0, st, p);
-    else EDGPU_LAUNCH(k_ingest<4>, dim3(nseg), dim3(kIngestThreads), 0, st, p);
-    if (p.npk && EDGPU_COPY_MODE(p) == 1) {
-        const uint32_t per = kCopyThreads / kCopyLanes;
-        EDGPU_LAUNCH(k_ingest_copy, dim3((p.npk + per - 1) / per), dim3(kCopyThreads), 0, st, p);
-    }
-#else
-    if (spec) EDGPU_LAUNCH((k_ingest<4, kIngestThreads, true>), dim3(nseg), dim3(kIngestThreads), 0, st, p);
-    else EDGPU_LAUNCH(k_ingest<4>, dim3(nseg), dim3(kIngestThreads), 0, st, p);
-#endif
+    const bool spec = !p.tcp_groups && !p.src_addr && p.spec_min && p.npk >= (uint64_t)p.spec_min * nseg;
+    if (spec) EDGPU_LAUNCH(k_ingest<true>, dim3(nseg), dim3(kIngestThreads), 0, st, p);
+    else EDGPU_LAUNCH(k_ingest<false>, dim3(nseg), dim3(kIngestThreads), 0, st, p);
     return hipGetLastError();
 }
 hipError_t launch_image(const ImageParams& p, int phase, hipStream_t st) {
@@ -2962,118 +2240,19 @@ hipError_t launch_plan_pass(const PlanParams& p, hipStream_t st) {
     EDGPU_LAUNCH(k_plan_pass, dim3(max(p.T.nsub_blocks, 1u)), dim3(256), 0, st, p);
     return hipGetLastError();
 }
-// Fan-out variants (EDGPU_FANOUT env var, for A/B measurement).  Each entry: kernel,
-// threads per workgroup, packets per work item.
+// The two fan-out kernels (EDGPU_FANOUT=0|1 pins one).  Each entry: kernel, threads per
+// workgroup, packets per work item.
 static int occupancy_of(const void* fn, int threads, int lds) {
     int blocks = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, threads, lds) != hipSuccess) return 1;
     return blocks > 0 ? blocks : 1;
 }
-struct FanoutVariant { const void* fn; int threads; int chunk; int lds; int max_wg_per_cu = 0; };
-#ifdef EDGPU_AB_VARIANTS
+struct FanoutVariant { const void* fn; int threads; int chunk; int lds; };
 static const FanoutVariant kVariants[] = {
-    {(const void*)k_fanout3<1024, 32>, 1024, 32, fanout3_lds<1024, 32>()},          // 0 r01 LDS, aligned
-    {(const void*)k_fanout3<512, 16>, 512, 16, fanout3_lds<512, 16>()},             // 1
-    {(const void*)k_fanout4<1024, 32>, 1024, 32, fanout4_lds<1024, 32>()},          // 2 scalar headers, prefetch
-    {(const void*)k_fanout4<512, 32>, 512, 32, fanout4_lds<512, 32>()},             // 3
-    {(const void*)k_fanout4<1024, 16>, 1024, 16, fanout4_lds<1024, 16>()},          // 4
-    {(const void*)k_fanout4<512, 16>, 512, 16, fanout4_lds<512, 16>()},             // 5
-    {(const void*)k_fanout5<256, 32>, 256, 32, fanout5_lds<256, 32>()},             // 6 LDS-DMA, 4 waves/CU
-    {(const void*)k_fanout5<512, 32>, 512, 32, fanout5_lds<512, 32>()},             // 7
-    {(const void*)k_fanout5<128, 16>, 128, 16, fanout5_lds<128, 16>()},             // 8
-    {(const void*)k_fanout5<256, 16>, 256, 16, fanout5_lds<256, 16>()},             // 9
-    {(const void*)k_fanout4<1024, 32, 2>, 1024, 32, fanout4_lds<1024, 32>()},       // 10 nt arena stores
-    {(const void*)k_fanout4<1024, 32, 16>, 1024, 32, fanout4_lds<1024, 32>()},      // 11 sc1
-    {(const void*)k_fanout4<1024, 32, 17>, 1024, 32, fanout4_lds<1024, 32>()},      // 12 sc0 sc1
-    {(const void*)k_fanout4<1024, 32, 2, 1>, 1024, 32, fanout4_lds<1024, 32>()},    // 13 nt arena + descriptors
-    {(const void*)k_fanout4<1024, 32, 2, 1, 2>, 1024, 32, fanout4_lds<1024, 32>()}, // 14 ... + nt chunk loads
-    {(const void*)k_fanout4<1024, 32, 2, 0, 2>, 1024, 32, fanout4_lds<1024, 32>()}, // 15 nt arena + nt loads
-    {(const void*)k_fanout5<256, 32, 2>, 256, 32, fanout5_lds<256, 32>()},          // 16 LDS-DMA + nt arena
-    {(const void*)k_fanout5<512, 32, 2>, 512, 32, fanout5_lds<512, 32>()},          // 17
-    {(const void*)k_fanout4<512, 32, 2>, 512, 32, fanout4_lds<512, 32>()},          // 18 nt, 512 threads
-    {(const void*)k_fanout4<1024, 16, 2>, 1024, 16, fanout4_lds<1024, 16>()},       // 19 nt, 16-packet chunks
-    {(const void*)k_fanout4<1024, 36, 2>, 1024, 36, fanout4_lds<1024, 36>()},       // 20 nt, 36 (2 WG/CU)
-    {(const void*)k_fanout4<1024, 48, 2>, 1024, 48, fanout4_lds<1024, 48>()},       // 21 nt, 48 (1 WG/CU)
-    {(const void*)k_fanout4<1024, 56, 2>, 1024, 56, fanout4_lds<1024, 56>()},       // 22 nt, 56 (1 WG/CU)
-    {(const void*)k_fanout4<1024, 56, 2, 0, 0, 4>, 1024, 56, fanout4_lds<1024, 56>()}, // 23 + 4-deep store loop
-    {(const void*)k_fanout4<1024, 56, 2, 0, 0, 2>, 1024, 56, fanout4_lds<1024, 56>()}, // 24 + 2-deep
-    {(const void*)k_fanout4<1024, 32, 2, 0, 0, 2>, 1024, 32, fanout4_lds<1024, 32>()}, // 25 32, 2-deep
-    {(const void*)k_fanout4<1024, 32, 2, 0, 0, 1, 8>, 1024, 32, fanout4_lds<1024, 32>()}, // 26 32, <= 64 VGPRs
-    {(const void*)k_fanout4<1024, 32, 2, 0, 0, 1, 0, 1>, 1024, 32, fanout4_lds<1024, 32>()}, // 27 row-mask patch
-    {(const void*)k_fanout4<1024, 56, 2, 0, 0, 1, 0, 1>, 1024, 56, fanout4_lds<1024, 56>()}, // 28 56, row-mask
-    {(const void*)k_fanout4<1024, 32, 2, 0, 0, 1, 0, 0, 1>, 1024, 32, fanout4_lds<1024, 32, 1>()}, // 29 LDS FanSub
-    {(const void*)k_fanout4<1024, 56, 2, 0, 0, 1, 0, 0, 1>, 1024, 56, fanout4_lds<1024, 56, 1>()}, // 30 56, LDS FanSub
-    {(const void*)k_fanout4<1024, 32, 2, 0, 0, 1, 0, 0, 0, 1>, 1024, 32, fanout4_lds<1024, 32>()}, // 31 dynamic items
-    {(const void*)k_fanout4<1024, 56, 2, 0, 0, 1, 0, 0, 0, 1>, 1024, 56, fanout4_lds<1024, 56>()}, // 32 56, dynamic
-    {(const void*)k_fanout4<1024, 32, 2, 0, 0, 1, 8, 0, 0, 1>, 1024, 32, fanout4_lds<1024, 32>()}, // 33 32, <= 64 VGPRs, dynamic
-    {(const void*)k_fanout4<1024, 48, 2, 0, 0, 1, 0, 0, 0, 1>, 1024, 48, fanout4_lds<1024, 48>()}, // 34 48, dynamic
-    {(const void*)k_fanout4<1024, 32, 2, 0, 0, 1, 0, 0, 0, 1, 1>, 1024, 32, fanout4_lds<1024, 32>()}, // 35 dyn, patch path always
-    {(const void*)k_fanout4<1024, 32, 2, 0, 0, 1, 0, 0, 0, 1, 2>, 1024, 32, fanout4_lds<1024, 32>()}, // 36 dyn, s_sleep per row
-    {(const void*)k_fanout4<1024, 32, 2, 0, 0, 1, 0, 0, 0, 1, 0, 1>, 1024, 32, fanout4_lds<1024, 32>()}, // 37 dyn, two windows at once
-    {(const void*)k_fanout4<1024, 56, 2, 0, 0, 1, 0, 0, 0, 1, 0, 1>, 1024, 56, fanout4_lds<1024, 56>()}, // 38 56, dyn, two windows
-    {(const void*)k_fanout6<1024, 32>, 1024, 32, fanout6_lds<1024, 32>()},          // 39 two images, one barrier per item
-    {(const void*)k_fanout6<1024, 16>, 1024, 16, fanout6_lds<1024, 16>()},          // 40 same, 16-packet chunks (2 WG/CU)
-    {(const void*)k_fanout6<1024, 18>, 1024, 18, fanout6_lds<1024, 18>()},          // 41 18 packets (2 WG/CU)
-    {(const void*)k_fanout6<1024, 12>, 1024, 12, fanout6_lds<1024, 12>()},          // 42 12 packets (2 WG/CU)
-    {(const void*)k_fanout6<512, 16>, 512, 16, fanout6_lds<512, 16>()},             // 43 16 packets, 512 threads
-    {(const void*)k_fanout6<1024, 16>, 1024, 16, fanout6_lds<1024, 16>(), 1},       // 44 = 40 at one workgroup per CU
-    {(const void*)k_fanout6<1024, 18>, 1024, 18, fanout6_lds<1024, 18>(), 1},       // 45 = 41 at one workgroup per CU
-    {(const void*)k_fanout4<1024, 16, 2, 0, 0, 1, 0, 0, 0, 1>, 1024, 16, fanout4_lds<1024, 16>()}, // 46 16, dynamic (k_fanout4)
-    {(const void*)k_fanout4<1024, 16, 2, 0, 0, 1, 0, 1, 0, 1>, 1024, 16, fanout4_lds<1024, 16>()}, // 47 16, dynamic, row-mask patch
-    {(const void*)k_fanout4<1024, 24, 2, 0, 0, 1, 0, 0, 0, 1>, 1024, 24, fanout4_lds<1024, 24>()}, // 48 24, dynamic
-    {(const void*)k_fanout4<1024, 24, 2, 0, 0, 1, 0, 1, 0, 1>, 1024, 24, fanout4_lds<1024, 24>()}, // 49 24, dynamic, row-mask patch
-    {(const void*)k_fanout6<1024, 16, 2, 1>, 1024, 16, fanout6_lds<1024, 16>()},    // 50 16, per-packet patch
-    {(const void*)k_fanout6<1024, 32, 2, 1>, 1024, 32, fanout6_lds<1024, 32>()},    // 51 32, per-packet patch
-    {(const void*)k_fanout6<1024, 14>, 1024, 14, fanout6_lds<1024, 14>()},          // 52 14 packets
-    {(const void*)k_fanout6<1024, 20>, 1024, 20, fanout6_lds<1024, 20>()},          // 53 20
-    {(const void*)k_fanout6<1024, 22>, 1024, 22, fanout6_lds<1024, 22>()},          // 54 22 (a C2 window: 2 rows)
-    {(const void*)k_fanout6<1024, 23>, 1024, 23, fanout6_lds<1024, 23>()},          // 55 23
-    {(const void*)k_fanout6<768, 16>, 768, 16, fanout6_lds<768, 16>()},             // 56 768 threads: a C2 window in 2 rows
-    {(const void*)k_fanout6<768, 18>, 768, 18, fanout6_lds<768, 18>()},             // 57
-    {(const void*)k_fanout6<896, 16>, 896, 16, fanout6_lds<896, 16>()},             // 58
-    {(const void*)k_fanout6<768, 12>, 768, 12, fanout6_lds<768, 12>()},             // 59
-    {(const void*)k_fanout6<1024, 16, 2, 0, 1>, 1024, 16, fanout6_lds<1024, 16>()}, // 60 16, FanSub one window ahead
-    {(const void*)k_fanout6<1024, 32, 2, 0, 1>, 1024, 32, fanout6_lds<1024, 32>()}, // 61 32, same
-    {(const void*)k_fanout6<1024, 16, 2, 0, 0, 1>, 1024, 16, fanout6_lds<1024, 16>()}, // 62 16, branchy patch
-    {(const void*)k_fanout6<1024, 32, 2, 0, 0, 1>, 1024, 32, fanout6_lds<1024, 32>()}, // 63 32, branchy patch
-};
-static const char* const kVariantNames[] = {"k_fanout3<1024,32>", "k_fanout3<512,16>", "k_fanout4<1024,32>",
-                                            "k_fanout4<512,32>", "k_fanout4<1024,16>", "k_fanout4<512,16>",
-                                            "k_fanout5<256,32>", "k_fanout5<512,32>", "k_fanout5<128,16>", "k_fanout5<256,16>",
-                                            "k_fanout4<1024,32,nt>", "k_fanout4<1024,32,sc1>", "k_fanout4<1024,32,sc0sc1>",
-                                            "k_fanout4<1024,32,nt,ntdesc>", "k_fanout4<1024,32,nt,ntdesc,ntload>",
-                                            "k_fanout4<1024,32,nt,ntload>", "k_fanout5<256,32,nt>", "k_fanout5<512,32,nt>",
-                                            "k_fanout4<512,32,nt>", "k_fanout4<1024,16,nt>",
-                                            "k_fanout4<1024,36,nt>", "k_fanout4<1024,48,nt>", "k_fanout4<1024,56,nt>",
-                                            "k_fanout4<1024,56,nt,su4>", "k_fanout4<1024,56,nt,su2>",
-                                            "k_fanout4<1024,32,nt,su2>", "k_fanout4<1024,32,nt,wpe8>",
-                                            "k_fanout4<1024,32,nt,rowmask>", "k_fanout4<1024,56,nt,rowmask>",
-                                            "k_fanout4<1024,32,nt,ldsfansub>", "k_fanout4<1024,56,nt,ldsfansub>",
-                                            "k_fanout4<1024,32,nt,dyn>", "k_fanout4<1024,56,nt,dyn>",
-                                            "k_fanout4<1024,32,nt,wpe8,dyn>", "k_fanout4<1024,48,nt,dyn>",
-                                            "k_fanout4<1024,32,nt,dyn,patchall>", "k_fanout4<1024,32,nt,dyn,sleep>",
-                                            "k_fanout4<1024,32,nt,dyn,2win>", "k_fanout4<1024,56,nt,dyn,2win>",
-                                            "k_fanout6<1024,32,nt,dyn>", "k_fanout6<1024,16,nt,dyn>",
-                                            "k_fanout6<1024,18,nt,dyn>", "k_fanout6<1024,12,nt,dyn>", "k_fanout6<512,16,nt,dyn>",
-                                            "k_fanout6<1024,16,nt,dyn,1wg>", "k_fanout6<1024,18,nt,dyn,1wg>",
-                                            "k_fanout4<1024,16,nt,dyn>", "k_fanout4<1024,16,nt,rowmask,dyn>",
-                                            "k_fanout4<1024,24,nt,dyn>", "k_fanout4<1024,24,nt,rowmask,dyn>",
-                                            "k_fanout6<1024,16,nt,dyn,pp>", "k_fanout6<1024,32,nt,dyn,pp>",
-                                            "k_fanout6<1024,14,nt,dyn>", "k_fanout6<1024,20,nt,dyn>",
-                                            "k_fanout6<1024,22,nt,dyn>", "k_fanout6<1024,23,nt,dyn>",
-                                            "k_fanout6<768,16,nt,dyn>", "k_fanout6<768,18,nt,dyn>",
-                                            "k_fanout6<896,16,nt,dyn>", "k_fanout6<768,12,nt,dyn>",
-                                            "k_fanout6<1024,16,nt,dyn,pf>", "k_fanout6<1024,32,nt,dyn,pf>",
-                                            "k_fanout6<1024,16,nt,dyn,bp>", "k_fanout6<1024,32,nt,dyn,bp>"};
-#else
-// The shipped library: the two defaults.  The measurement build above keeps
-// their numbers (31 and 40) and every variant they were chosen over.
-static const FanoutVariant kVariants[] = {
-    {(const void*)k_fanout4<1024, 32, 2, 0, 0, 1, 0, 0, 0, 1>, 1024, 32, fanout4_lds<1024, 32>()}, // 0 = AB 31
-    {(const void*)k_fanout6<1024, 16>, 1024, 16, fanout6_lds<1024, 16>()},                           // 1 = AB 40
+    {(const void*)k_fanout4<1024, 32>, 1024, 32, fanout4_lds<1024, 32>()},
+    {(const void*)k_fanout6<1024, 16>, 1024, 16, fanout6_lds<1024, 16>()},
 };
 static const char* const kVariantNames[] = {"k_fanout4<1024,32,nt,dyn>", "k_fanout6<1024,16,nt,dyn>"};
-#endif
 static const int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 static_assert(sizeof(kVariantNames) / sizeof(kVariantNames[0]) == sizeof(kVariants) / sizeof(kVariants[0]),
               "one name per fan-out variant");
@@ -3082,21 +2261,9 @@ static_assert(sizeof(kVariantNames) / sizeof(kVariantNames[0]) == sizeof(kVarian
 // mode), k_fanout4<1024,32> when some do (RTSP-interleaved channel byte or a rewrite).  The
 // 16-packet chunks are ~4 % faster on identity windows but ~25 % slower through the patch path
 // (profiles/r02z9_*).
-#ifdef EDGPU_AB_VARIANTS
-static const int kDefaultVariant = 31;   // k_fanout4<1024,32,nt,dyn>: the patching default
-static const int kDefaultPlain = 40;     // k_fanout6<1024,16,nt,dyn>: every sub-stream identity UDP
-static const int kFirstRewriting = 2;    // k_fanout3 (0, 1) reads SubDev directly and has no rewrite stage
-#else
-static const int kDefaultVariant = 0;
-static const int kDefaultPlain = 1;
-static const int kFirstRewriting = 0;
-#endif
+static const int kDefaultVariant = 0;    // k_fanout4<1024,32,nt,dyn>: the patching default
+static const int kDefaultPlain = 1;      // k_fanout6<1024,16,nt,dyn>: every sub-stream identity UDP
 int fanout_default(bool patching) { return patching ? kDefaultVariant : kDefaultPlain; }
-// edgpu_subscriber_rewrite refuses a variant without a rewrite stage
-bool fanout_rewrites(int variant) {
-    if (variant < 0 || variant >= kNumVariants) variant = kDefaultVariant;
-    return variant >= kFirstRewriting;
-}
 int fanout_chunk(int variant) {
     if (variant < 0 || variant >= kNumVariants) variant = kDefaultVariant;
     return kVariants[variant].chunk;
@@ -3107,12 +2274,11 @@ const char* fanout_name(int variant) {
 }
 hipError_t launch_fanout(const FanoutParams& p, int variant, int num_cus, hipStream_t st) {
     if (variant < 0 || variant >= kNumVariants) variant = kDefaultVariant;
-    static int occ[64] = {0};
+    static int occ[kNumVariants] = {0};
     const FanoutVariant& v = kVariants[variant];
     if (!occ[variant]) {
         if (v.lds > 48 * 1024) (void)hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds);
         occ[variant] = occupancy_of(v.fn, v.threads, v.lds);
-        if (v.max_wg_per_cu && occ[variant] > v.max_wg_per_cu) occ[variant] = v.max_wg_per_cu;
     }
     void* args[] = {(void*)&p};
     ++tl_launches;

@@ -4,21 +4,10 @@
 #include "edgpu.h"
 #include "edgpu_device.h"
 
-// Measurement builds (-DEDGPU_AB_VARIANTS: `make -C easydarwin_amd/csrc ab` ->
-// easydarwin_amd/ab/libedgpu_ab.so, loaded with EDGPU_LIB) carry every fan-out variant ever
-// measured, the EDGPU_ABLATE skip-work bits and the alternative ingest copy paths
-// (EDGPU_INGEST, EDGPU_INGEST_TCP).  The shipped libedgpu.so has the two default fan-out
-// kernels and no skip-work branch: these knobs are compile-time constants there.
-#ifdef EDGPU_AB_VARIANTS
-#define EDGPU_ABL(P) ((P).ablate)
-#define EDGPU_COPY_MODE(P) ((P).copy_mode)
-#define EDGPU_TCP_COPY(P) ((P).tcp_copy)
-#else
-#define EDGPU_ABL(P) 0u
-#define EDGPU_COPY_MODE(P) 0u
-#define EDGPU_TCP_COPY(P) 3u
-#endif
-
+// The library has the two fan-out kernels and one ingest kernel it runs.  The measurement build
+// (`make ab`: every fan-out variant ever measured, the EDGPU_ABLATE skip-work bits, the
+// alternative ingest copy paths EDGPU_INGEST / EDGPU_INGEST_TCP) was removed; its code is in git
+// at commit 0dd0039, its numbers in docs/MEASUREMENT_HISTORY.md (A.1-A.3).
 namespace edgpu {
 
 // Kernel launches made on this thread (edgpu_counters.kernel_launches: the engine adds what each
@@ -32,11 +21,8 @@ extern thread_local uint64_t tl_launches;
 
 // Interleaved frames a k_ingest wave copies per round (all their loads before the first
 // store): 4 since the copy is specialised on the frame's word offset (128 VGPRs, 4 waves per
-// SIMD); it was 2 (tools/build_ingest_ab.sh builds others)
-#ifndef EDGPU_TCP_TD
-#define EDGPU_TCP_TD 4
-#endif
-constexpr uint32_t kTcpFramesPerRound = EDGPU_TCP_TD;
+// SIMD); it was 2
+constexpr uint32_t kTcpFramesPerRound = 4;
 
 struct TcpGroup;
 struct TcpChunkRes;
@@ -52,15 +38,8 @@ struct IngestParams {
     SessionDev* sessions;
     SenderDev* senders;
     StreamDev* streams;
-    CopyJob* jobs;          // per desc: slot copy for k_ingest_copy
     uint32_t npk;           // descriptors in the batch
     uint32_t spec_min;      // the speculative copy from this many packets per segment on (0: never)
-    uint32_t copy_mode;     // 0: copy inside k_ingest, 1: k_ingest_copy (EDGPU_INGEST)
-    uint32_t tcp_copy;      // frames in the TCP byte stream: 1 one aligned load per word + the
-                            // neighbour word by DPP, 2 the same with two frames per wave round
-                            // (default); 0 two aligned loads per word (EDGPU_INGEST_TCP)
-    uint32_t ablate;        // timing experiments only (EDGPU_ABLATE bits 4-7: 16 no totals, 32 no slot
-                            // copy, 64 no per-sender scans)
     uint32_t host_epoch;    // != 0: the blob is a host batch the host keeps for the tick; record each
                             // packet's slot and the batch (edgpu_fanout_sources)
     TickTotals* totals;
@@ -114,7 +93,6 @@ struct FanoutParams {
     uint64_t arena_words;       // capacities: stores outside them are dropped and flagged
     uint32_t max_desc;
     TickTotals* totals;
-    uint32_t ablate;            // timing-only builds: bit0 skip descriptors, bit1 skip arena stores
 };
 
 // ---- RTSP-interleaved ingest ('$'-deframe of pusher TCP reads, edgpu_ingest_interleaved) ----

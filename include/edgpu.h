@@ -717,7 +717,9 @@ int  edgpu_arena_gather(edgpu_ctx* ctx, const edgpu_fanout_result* r, const edgp
                         void* dst, uint64_t dst_cap);
 
 /* Name of the fan-out copy kernel of this context's last edgpu_fanout (before the first: the one
- * it would launch), for measurement reports.  Unless EDGPU_FANOUT selects one, a tick takes the
+ * it would launch), for measurement reports.  There are two (every other variant and the
+ * measurement build that carried them were removed; git commit 0dd0039 has their code).  Unless
+ * EDGPU_FANOUT=0|1 pins one, a tick takes the
  * 32-packet-chunk kernel when any active sub-stream is RTSP-interleaved or rewrites (a per-output
  * patch) or when the outputs added since the last tick hold a quarter or more of its sub-stream
  * rows and at least 4096 of them (a join burst), else the 16-packet-chunk one; see DESIGN.md §3. */
