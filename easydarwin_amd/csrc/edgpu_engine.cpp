@@ -286,9 +286,10 @@ struct edgpu_ctx {
     // edgpu_stream_stats_enable)
     // (ring 5, a tap drain's kernels: by the first edgpu_tap_enable)
     // (ring 6, a transport-stream mux's kernels: by the first edgpu_ts_mux)
-    hipEvent_t hist[7][kHist][2] = {};
-    uint32_t hist_n[7] = {0, 0, 0, 0, 0, 0, 0};   // pairs recorded (monotonic sequence numbers)
-    uint32_t hist_rd[7] = {0, 0, 0, 0, 0, 0, 0};  // pairs already returned by edgpu_kernel_times
+    // (ring 7, a fragmented-MP4 mux's kernels: by the first edgpu_mp4_mux)
+    hipEvent_t hist[8][kHist][2] = {};
+    uint32_t hist_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // pairs recorded (monotonic sequence numbers)
+    uint32_t hist_rd[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // pairs already returned by edgpu_kernel_times
     // Borrowed end points.  A whole-tick entry (ring 1) ends at its copy kernel's end event
     // (ring 0 sequence number in tick_end[slot]); a keyframe entry (ring 3) starts at the end
     // event of the ingest it indexes (ring 2 sequence number in kf_from[slot]) when nothing ran
@@ -297,7 +298,7 @@ struct edgpu_ctx {
     static const uint32_t kOwnStart = 0xFFFFFFFFu;
     uint32_t tick_end[kHist] = {};
     uint32_t kf_from[kHist] = {};
-    uint32_t last_seq[7] = {0, 0, 0, 0, 0, 0, 0}; // each ring's newest complete pair (edgpu_last_timings)
+    uint32_t last_seq[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // each ring's newest complete pair (edgpu_last_timings)
     bool kf_share = false;                  // the last ingest's end event may start the keyframe entry
     uint64_t fanout_launches = 0;
     int64_t last_now = 0;               // clock of the last edgpu_fanout (backpressure reports)
@@ -349,6 +350,20 @@ struct edgpu_ctx {
     DevVec<uint32_t> d_ts_base;
     DevVec<edgpu_ts_unit> d_ts_rows;
     uint8_t* d_ts_fixed = nullptr;          // TsPlace, then the PAT and PMT packet templates
+    // the fragmented-MP4 mux (edgpu_mp4_mux): staging and work buffers only, allocated by the first
+    // call and sized from each call's es_bytes and n_units; the state rows are the caller's
+    DevVec<uint8_t> d_mp4_es, d_mp4_out;
+    DevVec<uint32_t> d_mp4_bitmap, d_mp4_chunks, d_mp4_lens;
+    DevVec<edgpu_tap_unit> d_mp4_units_in;
+    DevVec<Mp4Range> d_mp4_ranges;
+    DevVec<edgpu_mp4_state> d_mp4_states;   // 2 x n_streams: the caller's rows, the new rows
+    DevVec<Mp4Rec> d_mp4_recs;
+    DevVec<Mp4FragRec> d_mp4_frecs;
+    DevVec<Mp4StreamRec> d_mp4_srecs;
+    DevVec<Mp4Samp> d_mp4_samps;
+    DevVec<edgpu_mp4_sample> d_mp4_rows;
+    DevVec<edgpu_mp4_frag> d_mp4_frags;
+    Mp4Place* d_mp4_place = nullptr;
     DevVec<SubDev> d_subs;
     DevVec<uint32_t> d_sub_index;
     DevVec<uint32_t> d_sub_range;
@@ -660,6 +675,10 @@ int edgpu_ctx_destroy(edgpu_ctx* x) {
     x->d_ts_es.release(); x->d_ts_out.release(); x->d_ts_units_in.release(); x->d_ts_ranges.release();
     x->d_ts_states.release(); x->d_ts_recs.release(); x->d_ts_base.release(); x->d_ts_rows.release();
     if (x->d_ts_fixed) (void)hipFree(x->d_ts_fixed);
+    x->d_mp4_es.release(); x->d_mp4_out.release(); x->d_mp4_bitmap.release(); x->d_mp4_chunks.release(); x->d_mp4_lens.release();
+    x->d_mp4_units_in.release(); x->d_mp4_ranges.release(); x->d_mp4_states.release(); x->d_mp4_recs.release();
+    x->d_mp4_frecs.release(); x->d_mp4_srecs.release(); x->d_mp4_samps.release(); x->d_mp4_rows.release(); x->d_mp4_frags.release();
+    if (x->d_mp4_place) (void)hipFree(x->d_mp4_place);
     x->d_carry.release(); x->d_tcp_groups.release(); x->d_tcp_reads.release(); x->d_tcp_chunk_group.release();
     x->d_tcp_ncand.release(); x->d_tcp_cands.release(); x->d_tcp_links.release(); x->d_tcp_chunkres.release();
     x->d_tcp_results.release(); x->d_tcp_offs.release(); x->d_tcp_stage.release(); x->d_blocked.release();
@@ -2708,8 +2727,132 @@ int edgpu_ts_mux(edgpu_ctx* x, const edgpu_ts_config* cfg, const void* es, uint6
     return EDGPU_OK;
 }
 
+// ---- Fragmented-MP4 mux of tapped access units (edgpu_mp4_mux; edgpu_mp4.hip) ----
+int edgpu_mp4_mux(edgpu_ctx* x, const edgpu_mp4_config* cfg, const void* es, uint64_t es_bytes, int es_kind,
+                  const edgpu_tap_unit* units, uint32_t n_units, const edgpu_tap_stream* streams, uint32_t n_streams,
+                  edgpu_mp4_state* states, void* out, uint64_t out_cap, int out_kind, edgpu_mp4_sample* samples,
+                  edgpu_mp4_frag* frags, uint32_t frag_cap, edgpu_mp4_result* result) {
+    if (!x || !result || (!es && es_bytes) || (!out && out_cap) || (!units && n_units) || (!samples && n_units) ||
+        (!streams && n_streams) || (!states && n_streams) || (!frags && frag_cap))
+        return fail(EDGPU_BAD_ARGUMENT, "bad argument");
+    for (int k : {es_kind, out_kind})
+        if (k != EDGPU_PTR_HOST && k != EDGPU_PTR_DEVICE && k != EDGPU_PTR_PINNED) return fail(EDGPU_BAD_ARGUMENT, "bad pointer kind");
+    const bool device_es = es_kind == EDGPU_PTR_DEVICE, device_out = out_kind == EDGPU_PTR_DEVICE;
+    if ((device_es && ((uintptr_t)es & 15)) || (device_out && ((uintptr_t)out & 15)))
+        return fail(EDGPU_BAD_ARGUMENT, "device `es` and `out` must be 16-B aligned");
+    edgpu_mp4_config c;
+    memset(&c, 0, sizeof(c));
+    if (cfg) c = *cfg;
+    if (!c.default_duration) c.default_duration = 3600;
+    if (c.flags) return fail(EDGPU_BAD_ARGUMENT, "bad fragmented-MP4 configuration: no flags are defined");
+    // the rows the kernels index by: checked here, on the host
+    for (uint32_t i = 0; i < n_units; i++) {
+        if (units[i].stream >= n_streams) return fail(EDGPU_BAD_ARGUMENT, "a unit's stream index is out of range");
+        if (units[i].offset > es_bytes || units[i].bytes > es_bytes - units[i].offset)
+            return fail(EDGPU_BAD_ARGUMENT, "a unit reaches outside the ES bytes");
+    }
+    std::vector<Mp4Range> ranges(n_streams);
+    uint64_t covered = 0, next = 0, most = 0;       // `most`: the bytes the output can need at the most
+    for (uint32_t s = 0; s < n_streams; s++) {
+        const uint64_t first = streams[s].unit_first, count = streams[s].unit_count;
+        if (first + count > n_units) return fail(EDGPU_BAD_ARGUMENT, "a stream's unit range reaches outside the units");
+        if (count) {
+            if (first < next) return fail(EDGPU_BAD_ARGUMENT, "the streams' unit ranges must ascend without overlap");
+            next = first + count;
+        }
+        uint64_t total = 0;
+        for (uint64_t i = first; i < first + count; i++) total += units[i].bytes;
+        if (total >= (1ull << 31)) return fail(EDGPU_BAD_ARGUMENT, "a stream's units total 2^31 bytes or more");
+        if (total + 108 * count >= (1ull << 32))   // fragment sizes and offsets within a run are 32-bit
+            return fail(EDGPU_BAD_ARGUMENT, "a stream's run could reach 2^32 bytes");
+        ranges[s] = Mp4Range{(uint32_t)first, (uint32_t)count, (uint32_t)(covered + s), 0u};
+        covered += count;
+        most += total + 108 * count + 16;
+    }
+    memset(result, 0, sizeof(*result));
+    result->units = n_units; result->streams = n_streams;
+    if (!n_streams) {
+        if (n_units) memset(samples, 0, (size_t)n_units * sizeof(edgpu_mp4_sample));
+        return EDGPU_OK;
+    }
+    DEVICE_ENTER(x);
+    if (!x->hist[7][0][0])
+        for (auto& s : x->hist[7]) for (auto& e : s) HIP_CHECK(hipEventCreate(&e));
+    if (!x->d_mp4_place && dmalloc(&x->d_mp4_place, sizeof(Mp4Place)) != hipSuccess)
+        return fail(EDGPU_OUT_OF_MEMORY, "fragmented-MP4 mux staging");
+    const uint64_t nwords = (es_bytes + 31) / 32, nchunks = (nwords + kMp4ChunkWords - 1) / kMp4ChunkWords;
+    const size_t nu = std::max<uint32_t>(n_units, 1);
+    HIP_CHECK(x->d_mp4_units_in.reserve(nu, x->stream));
+    HIP_CHECK(x->d_mp4_recs.reserve(nu, x->stream));
+    HIP_CHECK(x->d_mp4_samps.reserve(nu, x->stream));
+    HIP_CHECK(x->d_mp4_rows.reserve(nu, x->stream));
+    HIP_CHECK(x->d_mp4_frags.reserve(nu, x->stream));
+    HIP_CHECK(x->d_mp4_frecs.reserve((size_t)n_units + n_streams, x->stream));
+    HIP_CHECK(x->d_mp4_ranges.reserve(n_streams, x->stream));
+    HIP_CHECK(x->d_mp4_srecs.reserve(n_streams, x->stream));
+    HIP_CHECK(x->d_mp4_states.reserve(2 * (size_t)n_streams, x->stream));
+    HIP_CHECK(x->d_mp4_bitmap.reserve(nwords + 1, x->stream));
+    HIP_CHECK(x->d_mp4_chunks.reserve(nchunks + 1, x->stream));
+    HIP_CHECK(x->d_mp4_lens.reserve(es_bytes / 4 + 1, x->stream));
+    if (!device_es) HIP_CHECK(x->d_mp4_es.reserve(es_bytes + 16, x->stream));
+    // staging for the most the units can need, so the verdict never depends on the staging
+    if (!device_out) HIP_CHECK(x->d_mp4_out.reserve(std::max<uint64_t>(std::min<uint64_t>(out_cap, most), 16), x->stream));
+    if (n_units) HIP_CHECK(hipMemcpyAsync(x->d_mp4_units_in.ptr, units, (size_t)n_units * sizeof(edgpu_tap_unit), hipMemcpyHostToDevice, x->stream));
+    HIP_CHECK(hipMemcpyAsync(x->d_mp4_ranges.ptr, ranges.data(), (size_t)n_streams * sizeof(Mp4Range), hipMemcpyHostToDevice, x->stream));
+    HIP_CHECK(hipMemcpyAsync(x->d_mp4_states.ptr, states, (size_t)n_streams * sizeof(edgpu_mp4_state), hipMemcpyHostToDevice, x->stream));
+    if (!device_es && es_bytes) HIP_CHECK(hipMemcpyAsync(x->d_mp4_es.ptr, es, es_bytes, hipMemcpyHostToDevice, x->stream));
+    if (covered != n_units) HIP_CHECK(hipMemsetAsync(x->d_mp4_recs.ptr, 0, (size_t)n_units * sizeof(Mp4Rec), x->stream));
+    HIP_CHECK(wsync(x, x->stream));             // `ranges` is on the stack
+    Mp4Params p;
+    p.es = device_es ? (const uint8_t*)es : x->d_mp4_es.ptr;
+    p.es_bytes = es_bytes;
+    p.units = x->d_mp4_units_in.ptr; p.ranges = x->d_mp4_ranges.ptr;
+    p.states = x->d_mp4_states.ptr; p.new_states = x->d_mp4_states.ptr + n_streams;
+    p.bitmap = x->d_mp4_bitmap.ptr; p.chunk_first = x->d_mp4_chunks.ptr; p.lens = x->d_mp4_lens.ptr;
+    p.nwords = nwords; p.nchunks = nchunks;
+    p.recs = x->d_mp4_recs.ptr; p.frecs = x->d_mp4_frecs.ptr; p.srecs = x->d_mp4_srecs.ptr; p.samps = x->d_mp4_samps.ptr;
+    p.place = x->d_mp4_place;
+    p.out = device_out ? (uint8_t*)out : x->d_mp4_out.ptr;
+    p.rows = x->d_mp4_rows.ptr; p.frags = x->d_mp4_frags.ptr;
+    p.out_cap = out_cap;
+    p.time_offset = c.time_offset;
+    p.frag_cap = frag_cap; p.n_units = n_units; p.n_streams = n_streams; p.n_slots = n_units + n_streams;
+    p.max_samples = c.max_samples; p.default_duration = c.default_duration;
+    HIP_CHECK(hist_mark(x, 7, 0));
+    HIP_CHECK(launch_mp4_mux(p, (uint32_t)std::max(x->num_cus * 8, 1), x->stream));
+    HIP_CHECK(hist_mark(x, 7, 1));
+    Mp4Place pl;
+    {
+        Readback rb(x);
+        HIP_CHECK(rb.add(&pl, x->d_mp4_place, sizeof(pl)));
+        HIP_CHECK(rb.run());
+    }
+    result->bytes = pl.bytes; result->frags = pl.frags;
+    if (!pl.commit)
+        return fail(EDGPU_OUT_OVERFLOW, "fragmented-MP4 mux: " + std::to_string(pl.bytes) + " bytes and " + std::to_string(pl.frags) +
+                                        " fragment rows needed; nothing was written");
+    std::vector<Mp4StreamRec> runs;
+    if (!device_out) {                          // the bytes between two runs are not the caller's to lose
+        runs.resize(n_streams);
+        Readback rr(x);
+        HIP_CHECK(rr.add(runs.data(), x->d_mp4_srecs.ptr, (size_t)n_streams * sizeof(Mp4StreamRec)));
+        HIP_CHECK(rr.run());
+    }
+    Readback rb(x);
+    for (size_t s = 0; s < runs.size();) {
+        uint64_t a = runs[s].base, b = a + runs[s].bytes;
+        for (s++; s < runs.size() && runs[s].base == b; s++) b += runs[s].bytes;   // runs that touch: one copy
+        if (b > a) HIP_CHECK(rb.add((uint8_t*)out + a, x->d_mp4_out.ptr + a, b - a));
+    }
+    HIP_CHECK(rb.add(samples, x->d_mp4_rows.ptr, (size_t)n_units * sizeof(edgpu_mp4_sample)));
+    HIP_CHECK(rb.add(frags, x->d_mp4_frags.ptr, (size_t)pl.frags * sizeof(edgpu_mp4_frag)));
+    HIP_CHECK(rb.add(states, x->d_mp4_states.ptr + n_streams, (size_t)n_streams * sizeof(edgpu_mp4_state)));
+    HIP_CHECK(rb.run());
+    return EDGPU_OK;
+}
+
 int edgpu_kernel_times(edgpu_ctx* x, int which, float* out_ms, uint32_t max_n, uint32_t* out_n) {
-    if (!x || which < 0 || which > 6 || (!out_ms && max_n)) return fail(EDGPU_BAD_ARGUMENT, "bad argument");
+    if (!x || which < 0 || which > 7 || (!out_ms && max_n)) return fail(EDGPU_BAD_ARGUMENT, "bad argument");
     DEVICE_ENTER(x);
     HIP_CHECK(sync_all(x));
     const uint32_t n = std::min<uint32_t>(x->hist_n[which] - x->hist_rd[which], edgpu_ctx::kHist);

@@ -262,6 +262,61 @@ struct TsParams {
 };
 hipError_t launch_ts_mux(const TsParams& p, uint32_t pack_blocks, hipStream_t st);
 
+// The fragmented-MP4 mux (edgpu_mp4_mux, edgpu_mp4.hip): k_mp4_mark and k_mp4_resolve (flat over the
+// ES: the start codes and the distance from each to the next), k_mp4_plan (a wave per stream row),
+// k_mp4_place (one workgroup), k_mp4_rows (flat over fragments and units) and k_mp4_pack (flat over
+// the output's 16-B words).
+constexpr uint32_t kMp4None = 0xFFFFFFFFu;
+constexpr uint32_t kMp4ChunkWords = 64;     // bitmap words (of 32 ES bytes) one wave marks: a chunk is 2 KiB of ES
+struct Mp4Range { uint32_t first, count, slot, _pad; };   // slot: the row's first Mp4FragRec (the rows before it hold count + 1 each)
+struct Mp4Rec {                 // per unit, from k_mp4_plan; zero for a unit no row covers
+    uint64_t dts;
+    uint32_t slot;              // Mp4FragRec of its fragment
+    uint32_t poff;              // of its bytes in the fragment's mdat payload
+    uint32_t rank;              // its sample number within the stream's call
+    uint32_t duration;          // written by the lane of the stream's next sample
+    uint32_t flags;             // the sample row's | kind << 30: 0 uncovered, 1 no bytes, 2 a sample
+    uint32_t _pad;
+};
+static_assert(sizeof(Mp4Rec) == 32, "Mp4Rec layout");
+struct Mp4FragRec {             // per fragment start, and one more that closes the stream's last fragment
+    uint64_t tfdt;
+    uint64_t dsum;              // durations of the stream's samples before it
+    uint32_t unit_first;
+    uint32_t rank;              // samples of the stream before it
+    uint32_t bex;               // ES bytes of the stream before it
+    uint32_t prev_or;           // OR of the flags of the fragment it closes
+};
+static_assert(sizeof(Mp4FragRec) == 32, "Mp4FragRec layout");
+struct Mp4StreamRec { uint64_t bytes, base; uint32_t nfrags, fbase; };
+struct Mp4Samp { uint64_t off; uint32_t unit, _pad; };      // a stream's samples in order: offset in the stream's run
+struct Mp4Place { uint64_t bytes; uint32_t frags, commit; };
+struct Mp4Params {
+    const uint8_t* es;
+    uint64_t es_bytes;
+    const edgpu_tap_unit* units;
+    const Mp4Range* ranges;
+    const edgpu_mp4_state* states;
+    edgpu_mp4_state* new_states;
+    uint32_t* bitmap;           // nwords: bit b of word w: a start code begins at ES byte 32 w + b
+    uint32_t* chunk_first;      // nchunks: the chunk's first start code, relative, or kMp4None
+    uint32_t* lens;             // es_bytes / 4 + 1: at [q >> 2], the bytes from start code q's end to the next start code (or the ES end)
+    uint64_t nwords, nchunks;
+    Mp4Rec* recs;               // n_units
+    Mp4FragRec* frecs;          // n_units + n_streams
+    Mp4StreamRec* srecs;        // n_streams
+    Mp4Samp* samps;             // n_units
+    Mp4Place* place;
+    uint8_t* out;
+    edgpu_mp4_sample* rows;     // n_units
+    edgpu_mp4_frag* frags;      // n_units (staging holds the most there can be)
+    uint64_t out_cap;
+    uint64_t time_offset;
+    uint32_t frag_cap, n_units, n_streams, n_slots;
+    uint32_t max_samples, default_duration;
+};
+hipError_t launch_mp4_mux(const Mp4Params& p, uint32_t flat_blocks, hipStream_t st);
+
 struct ImageParams {
     SenderDev* senders;
     SessionDev* sessions;

@@ -202,6 +202,13 @@ public:
     // DisableElementaryStream.
     typedef std::function<void(const edgpu_tap_stream& stream, const edgpu_ts_unit* units, const uint8_t* packets)> TsSink;
     int  DrainTransportStreams(const TsSink& sink, bool flush = false, const edgpu_ts_config* cfg = nullptr);
+    // The same drain muxed into movie fragments on the GPU (edgpu_mp4_mux): `sink` is called once per
+    // fragment, in output order, with the fragment's stream row, its row, the sample rows of the whole
+    // drain (frag.unit_first indexes them; offsets relative to `bytes`) and the output bytes.  The
+    // mux's state rows are held here by (session, track) and dropped by DisableElementaryStream.
+    typedef std::function<void(const edgpu_tap_stream& stream, const edgpu_mp4_frag& frag, const edgpu_mp4_sample* samples,
+                               const uint8_t* bytes)> Mp4Sink;
+    int  DrainFragments(const Mp4Sink& sink, bool flush = false, const edgpu_mp4_config* cfg = nullptr);
     // diagnostics: one wave on the engine stream waits `us` of the device clock (edgpu_debug_stall)
     int DebugStall(uint32_t us);
     // the message of the last ReflectPackets failure that happened on another thread than the
@@ -223,6 +230,7 @@ private:
     // a tick's first write to its backpressure report (waiters: fIdleCv on fEngineMu)
     std::mutex fEngineMu;
     std::vector<std::pair<uint64_t, edgpu_ts_state>> fTsStates;   // by session << 32 | track: DrainTransportStreams (fEngineMu)
+    std::vector<std::pair<uint64_t, edgpu_mp4_state>> fMp4States; // by session << 32 | track: DrainFragments (fEngineMu)
     std::vector<uint8_t> fStatsOn;                          // per session: EnableStreamStats (fEngineMu)
     uint32_t fNumStats = 0;
     int (*fSampleStats)(edgpu_ctx*, int64_t) = nullptr;     // edgpu_stream_stats_sample once enabled

@@ -48,6 +48,9 @@ EXPORTED = [
     "edgpu_stream_stats_get", "edgpu_session_bitrate",
     "edgpu_tap_enable", "edgpu_tap_disable", "edgpu_tap_drain", "edgpu_ts_mux",
 ]
+# the fragmented-MP4 entry points, listed apart: tests/test_abi.py compares EXPORTED with the names its
+# pattern finds in the header, and that pattern stops at a digit (tests/test_mp4_abi.py checks these)
+EXPORTED_MP4 = ["edgpu_mp4_mux", "edgpu_mp4_init"]
 IPC_HANDLE_BYTES = 64
 TCP_MESSAGE, TCP_DROPPED = 1, 2
 PKT_REMOTE_ODD = 1          # edgpu_pkt_desc.flags: a UDP datagram from an odd source port
@@ -216,6 +219,38 @@ class TsResult(C.Structure):
     _fields_ = [("bytes", C.c_uint64), ("units", C.c_uint32), ("streams", C.c_uint32)]
 
 
+class Mp4Config(C.Structure):
+    """edgpu_mp4_config: a field that is 0 takes its default."""
+    _fields_ = [("time_offset", C.c_uint64), ("max_samples", C.c_uint32), ("default_duration", C.c_uint32),
+                ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class Mp4State(C.Structure):
+    """edgpu_mp4_state: what the fragmented-MP4 mux carries per stream between calls; the caller holds it."""
+    _fields_ = [("ext_ts", C.c_uint64), ("origin", C.c_uint64), ("sequence", C.c_uint32), ("last_step", C.c_uint32),
+                ("started", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class Mp4Sample(C.Structure):
+    """edgpu_mp4_sample: where one input unit's sample is."""
+    _fields_ = [("offset", C.c_uint64), ("dts", C.c_uint64), ("bytes", C.c_uint32), ("duration", C.c_uint32),
+                ("flags", C.c_uint32), ("fragment", C.c_uint32)]
+
+
+class Mp4Frag(C.Structure):
+    """edgpu_mp4_frag: one moof + mdat."""
+    _fields_ = [("offset", C.c_uint64), ("tfdt", C.c_uint64), ("duration", C.c_uint64), ("bytes", C.c_uint32),
+                ("sequence", C.c_uint32), ("unit_first", C.c_uint32), ("samples", C.c_uint32), ("flags", C.c_uint32),
+                ("stream", C.c_uint32)]
+
+
+class Mp4Result(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("units", C.c_uint32), ("frags", C.c_uint32), ("streams", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
+MP4_NO_FRAGMENT = 0xFFFFFFFF
+
 TS_AUD, TS_NOAUD = 1, 2
 TS_PACKET = 188
 
@@ -233,6 +268,11 @@ assert TAP_UNIT_DTYPE.itemsize == C.sizeof(TapUnit) == 48 and TAP_STREAM_DTYPE.i
 TS_UNIT_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in TsUnit._fields_])
 TS_STATE_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in TsState._fields_])
 assert TS_UNIT_DTYPE.itemsize == C.sizeof(TsUnit) == 32 and TS_STATE_DTYPE.itemsize == C.sizeof(TsState) == 16
+MP4_STATE_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in Mp4State._fields_])
+MP4_SAMPLE_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in Mp4Sample._fields_])
+MP4_FRAG_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in Mp4Frag._fields_])
+assert MP4_STATE_DTYPE.itemsize == C.sizeof(Mp4State) == 32 and MP4_SAMPLE_DTYPE.itemsize == C.sizeof(Mp4Sample) == 32
+assert MP4_FRAG_DTYPE.itemsize == C.sizeof(Mp4Frag) == 48 and C.sizeof(Mp4Config) == 24 and C.sizeof(Mp4Result) == 24
 PKT_DTYPE = np.dtype([("slot", "<u4"), ("len", "<u2"), ("channel", "u1"), ("flags", "u1"),
                       ("arrival_ms", "<i8")])
 OUT_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u4"), ("packet_id", "<u4")])
@@ -357,6 +397,9 @@ def load(path: str = LIB_PATH):
         "edgpu_tap_disable": (I32, [P, U32, U32]),
         "edgpu_tap_drain": (I32, [P, U32, P, U64, I32, P, U32, P, U32, C.POINTER(TapResult)]),
         "edgpu_ts_mux": (I32, [P, C.POINTER(TsConfig), P, U64, I32, P, U32, P, U32, P, P, U64, I32, P, C.POINTER(TsResult)]),
+        "edgpu_mp4_mux": (I32, [P, C.POINTER(Mp4Config), P, U64, I32, P, U32, P, U32, P, P, U64, I32, P, P, U32,
+                                C.POINTER(Mp4Result)]),
+        "edgpu_mp4_init": (I32, [P, U32, P, U32, U32, P, U64, C.POINTER(U64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -394,6 +437,20 @@ def device_local_cpus(device: int = 0) -> list:
     n = C.c_uint32()
     _check(lib.edgpu_device_local_cpus(device, buf, cap, C.byref(n)))
     return [int(buf[i]) for i in range(min(n.value, cap))]
+
+
+def mp4_init(sps: bytes, pps: bytes, timescale: int = 0) -> bytes:
+    """The initialisation segment (ftyp + moov) for one H.264 track (edgpu_mp4_init): `sps` and `pps`
+    are one NAL each, without start code.  Host only: no context, no device."""
+    lib = load()
+    sps, pps = bytes(sps), bytes(pps)
+    n = C.c_uint64()
+    buf = C.create_string_buffer(1024 + len(sps) + len(pps))
+    rc = lib.edgpu_mp4_init(sps, len(sps), pps, len(pps), timescale, buf, len(buf), C.byref(n))
+    if rc != 0:
+        raise EdgpuError(rc, "edgpu_mp4_init: " + ("the buffer is too small" if rc == OUT_OVERFLOW else
+                                                  "not an SPS and a PPS, or the SPS does not parse"))
+    return buf.raw[:n.value]
 
 
 class Context:
@@ -447,6 +504,8 @@ class Context:
         self._ntracks.pop(session, None)
         for k in [k for k in getattr(self, "_ts_states", {}) if k[0] == session]:
             del self._ts_states[k]
+        for k in [k for k in getattr(self, "_mp4_states", {}) if k[0] == session]:
+            del self._mp4_states[k]
 
     def subscriber_add(self, session: int, transport: int = TRANSPORT_UDP) -> int:
         out = C.c_uint32()
@@ -640,6 +699,7 @@ class Context:
     def tap_disable(self, session: int, track: int):
         _check(self.lib.edgpu_tap_disable(self.h, session, track))
         getattr(self, "_ts_states", {}).pop((session, track), None)
+        getattr(self, "_mp4_states", {}).pop((session, track), None)
 
     def tap_drain_raw(self, flags, out_ptr, out_cap, ptr_kind, units: np.ndarray, streams: np.ndarray) -> tuple:
         """edgpu_tap_drain as it is: (status, TapResult)."""
@@ -729,6 +789,66 @@ class Context:
             self._ts_states[k] = states[i].copy()
         return out[:tres.bytes], ts_units, streams
 
+    def mp4_mux_raw(self, cfg, es_ptr, es_bytes, es_kind, units: np.ndarray, streams: np.ndarray, states: np.ndarray,
+                    out_ptr, out_cap, out_kind, samples: np.ndarray, frags: np.ndarray) -> tuple:
+        """edgpu_mp4_mux as it is: (status, Mp4Result).  `units` / `streams` are TAP_UNIT_DTYPE /
+        TAP_STREAM_DTYPE rows, `states` MP4_STATE_DTYPE rows (in / out), `samples` MP4_SAMPLE_DTYPE rows
+        (one per unit), `frags` MP4_FRAG_DTYPE rows (its length is frag_cap)."""
+        res = Mp4Result()
+        rc = self.lib.edgpu_mp4_mux(self.h, C.byref(cfg) if cfg is not None else None, C.c_void_p(es_ptr), es_bytes, es_kind,
+                                    _ptr(units) if len(units) else None, len(units),
+                                    _ptr(streams) if len(streams) else None, len(streams),
+                                    _ptr(states) if len(states) else None,
+                                    C.c_void_p(out_ptr), out_cap, out_kind,
+                                    _ptr(samples) if len(samples) else None,
+                                    _ptr(frags) if len(frags) else None, len(frags), C.byref(res))
+        return rc, res
+
+    def tap_drain_mp4(self, flush: bool = False, cfg=None):
+        """Drains every enabled tap into device memory and muxes the units into movie fragments there
+        (edgpu_tap_drain, edgpu_mp4_mux): (bytes, samples, frags, units, streams) -- a uint8 array
+        holding each stream's run of moof + mdat fragments, MP4_SAMPLE_DTYPE rows (one per drained
+        unit), MP4_FRAG_DTYPE rows in output order, and the drain's unit and stream rows.  The mux's
+        state rows are kept here by (session, track); tap_disable and session_remove drop them."""
+        if not hasattr(self, "_mp4_states"):
+            self._mp4_states = {}
+        if getattr(self, "_mp4_es", None) is None:
+            self._mp4_es = self.device_alloc(1 << 20)
+        caps = getattr(self, "_tap_caps", [1 << 20, 4096, 64])
+        for attempt in range(2):
+            units = np.zeros(caps[1], dtype=TAP_UNIT_DTYPE)
+            streams = np.zeros(caps[2], dtype=TAP_STREAM_DTYPE)
+            rc, res = self.tap_drain_raw(TAP_FLUSH if flush else 0, self._mp4_es.ptr, self._mp4_es.nbytes, PTR_DEVICE, units, streams)
+            if rc != OUT_OVERFLOW or attempt:
+                break
+            caps = [caps[0], max(caps[1], int(res.units)), max(caps[2], int(res.streams))]
+            self._tap_caps = caps
+            if res.bytes > self._mp4_es.nbytes:
+                self._mp4_es.free()
+                self._mp4_es = None
+                self._mp4_es = self.device_alloc(max(int(res.bytes), 2 * caps[0]))
+        _check(rc)
+        units, streams = units[:res.units], streams[:res.streams]
+        keys = [(int(st["session"]), int(st["track"])) for st in streams]
+        states = np.zeros(len(streams), dtype=MP4_STATE_DTYPE)
+        for i, k in enumerate(keys):
+            if k in self._mp4_states:
+                states[i] = self._mp4_states[k]
+        samples = np.zeros(len(units), dtype=MP4_SAMPLE_DTYPE)
+        frags = np.zeros(max(len(units), 1), dtype=MP4_FRAG_DTYPE)      # a fragment holds at least one unit
+        cap = getattr(self, "_mp4_cap", 1 << 20)
+        for attempt in range(2):
+            out = np.empty(cap, dtype=np.uint8)
+            rc, mres = self.mp4_mux_raw(cfg, self._mp4_es.ptr, int(res.bytes), PTR_DEVICE, units, streams, states,
+                                        out.ctypes.data, out.nbytes, PTR_HOST, samples, frags)
+            if rc != OUT_OVERFLOW or attempt:
+                break
+            cap = self._mp4_cap = max(int(mres.bytes), 2 * cap)
+        _check(rc)
+        for i, k in enumerate(keys):
+            self._mp4_states[k] = states[i].copy()
+        return out[:mres.bytes], samples, frags[:mres.frags], units, streams
+
     def debug_stall(self, us: int):
         """edgpu_debug_stall: one wave on the context stream waits `us` microseconds of the device
         clock -- work the GPU watchdog (watchdog_ms) can time out on."""
@@ -757,7 +877,7 @@ class Context:
 
     def kernel_times(self, which: int) -> list:
         """which: 0 fan-out kernel, 1 whole fan-out tick, 2 ingest, 3 keyframe index, 4 stream statistics,
-        5 a tap drain, 6 a transport-stream mux."""
+        5 a tap drain, 6 a transport-stream mux, 7 a fragmented-MP4 mux."""
         buf = (C.c_float * 256)()
         n = C.c_uint32()
         _check(self.lib.edgpu_kernel_times(self.h, which, buf, 256, C.byref(n)))

@@ -875,8 +875,8 @@ int  edgpu_session_bitrate(edgpu_ctx* ctx, uint32_t session, uint32_t* bps);
  * Between drains a tap carries its head, the previous good packet's sequence number, a
  * pending-damage bit and the counters.  Taps belong to the owning context: they do not travel in
  * session images, a replica session starts without them, edgpu_session_remove clears them.
- * Out of scope: MP4 muxing, audio, packetization-mode 2, H.265, reordering.  (The drained units as
- * an MPEG-2 transport stream: edgpu_ts_mux below.) */
+ * Out of scope: audio, packetization-mode 2, H.265, reordering.  (The drained units as an MPEG-2
+ * transport stream: edgpu_ts_mux below; as fragmented MP4: edgpu_mp4_mux.) */
 #define EDGPU_TAP_KEY       1u
 #define EDGPU_TAP_PARAMS    2u
 #define EDGPU_TAP_DAMAGED   4u
@@ -972,7 +972,7 @@ int  edgpu_tap_drain(edgpu_ctx* ctx, uint32_t flags, void* out, uint64_t out_cap
  * Configuration: a field that is 0 takes its default, so `flags` 0 means EDGPU_TS_AUD;
  * EDGPU_TS_NOAUD alone turns the delimiter off; pcr_lead 0 means 63000.  PIDs above 0x1FFF, equal
  * PIDs or unknown flag bits are EDGPU_BAD_ARGUMENT.
- * Out of scope: audio PIDs, DTS / B-frames, MP4 and fMP4, H.265, SCTE markers. */
+ * Out of scope: audio PIDs, DTS / B-frames, H.265, SCTE markers.  (Fragmented MP4: edgpu_mp4_mux.) */
 #define EDGPU_TS_AUD      1u
 #define EDGPU_TS_NOAUD    2u
 #define EDGPU_TS_PACKET 188u
@@ -1013,11 +1013,124 @@ int  edgpu_ts_mux(edgpu_ctx* ctx, const edgpu_ts_config* cfg /* NULL: defaults *
                   void* out, uint64_t out_cap, int out_kind,
                   edgpu_ts_unit* ts_units /* n_units */, edgpu_ts_result* result);
 
+/* ---- Fragmented MP4 (CMAF) mux of tapped access units ----
+ *
+ * edgpu_mp4_mux turns what edgpu_tap_drain returned into movie fragments (ISO/IEC 14496-12 moof +
+ * mdat, samples in the length-prefixed form of 14496-15) on the GPU: appended to the ftyp + moov of
+ * edgpu_mp4_init they are a recording that is valid after every fragment, and the same fragments are
+ * HLS fMP4 / CMAF segments (easydarwin_amd/mp4.py, hls.py).  As with edgpu_ts_mux the caller holds
+ * one edgpu_mp4_state row per stream (zero to start); the context keeps no table, and nothing is
+ * launched or allocated until the first call.  tests/mp4_model.py is the executable statement of
+ * the rules below.
+ *
+ *   Order.  The streams in row order, each stream's run at the next 16-B aligned offset of `out`
+ *     (the bytes between two runs are not written); a stream's fragments follow each other without
+ *     a gap, so a run is appended to a file as it is.  result->bytes is the end of the last row's
+ *     run.  The stream rows' unit ranges must ascend without overlap; a unit no row covers gets a
+ *     zero sample row.
+ *   Time.  ext is the RTP timestamp extended per stream exactly as in edgpu_ts_mux (signed 32-bit
+ *     steps; started == 0: ext = rtp_ts).  origin is ext at the stream's first unit ever;
+ *     dts = (ext - origin + time_offset) mod 2^64.  A unit with bytes == 0 carries no sample: it is
+ *     in no fragment, its row has fragment 0xFFFFFFFF, its dts and the tap unit's flags, and is
+ *     otherwise zero; it still advances ext and sets started.
+ *   Samples.  Each unit with ES bytes is one sample of the same size.  Every occurrence of
+ *     00 00 00 01 wholly inside the unit is a start code (so in 00 00 00 00 01 the first byte is
+ *     data, and 00 00 01 alone is data); it is replaced by the big-endian 32-bit count of bytes
+ *     from its end to the next start code or the unit's end.  Every other byte is copied.  A unit
+ *     with ES bytes that does not begin with a start code keeps the bytes before its first one
+ *     unchanged and its sample row gets EDGPU_TAP_DAMAGED.  All NALs stay in the sample.
+ *   Duration.  A sample's duration is the signed 64-bit difference of the stream's next sample's
+ *     ext (in the same call) to its own: 0 if not positive, 0xFFFFFFFF if above that.  last_step
+ *     becomes the last strictly positive (clamped) difference computed in the call and is unchanged
+ *     if there was none; then the stream's last sample of the call takes last_step if it is
+ *     non-zero, otherwise default_duration.  A fragment's tfdt comes from ext, never from summed
+ *     durations, so timing cannot drift; the last sample of a call may be off by the difference
+ *     between the guessed and the real step.
+ *   Fragments.  A stream's fragment starts at its first sample of the call, at every EDGPU_TAP_KEY
+ *     sample, and where the running fragment already holds max_samples samples.  Every call closes
+ *     its fragments.  sequence counts the stream's fragments from 1 across calls.
+ *   Bytes of a fragment of n samples, all fields big-endian: moof (88 + 12n bytes) = box header;
+ *     mfhd (16: version/flags 0, sequence_number); traf box header; tfhd (16: flags 0x020000
+ *     default-base-is-moof, track 1); tfdt (20: version 1, the u64 dts of the first sample); trun
+ *     (20 + 12n: version 0, flags 0x000701, sample_count, data_offset = 88 + 12n + 8, then per
+ *     sample duration, size, flags -- 0x02000000 for an EDGPU_TAP_KEY unit, 0x01010000 otherwise);
+ *     then mdat: u32 size 8 + the samples' bytes, 'mdat', the samples.
+ *   Rows.  A sample row: offset of the sample's bytes in `out`, its size, duration, flags (the tap
+ *     unit's, with DAMAGED as above), the index of its fragment row, its dts.  A fragment row:
+ *     offset and bytes of moof + mdat, tfdt, sequence, the unit index of its first sample, its
+ *     samples, the sum of their durations, the OR of its sample rows' flags (so EDGPU_TAP_KEY says
+ *     the fragment begins with a key unit), its stream row.  Fragment rows are in output order.
+ * Configuration: a field that is 0 takes its default (max_samples 0: no limit; default_duration
+ * 3600).  No flags are defined: a non-zero `flags` is EDGPU_BAD_ARGUMENT, as is a stream row whose
+ * units total 2^31 bytes or more, or whose run could reach 2^32 bytes (its units' bytes + 108 per
+ * unit: a fragment of one sample has 108 bytes of boxes).
+ * Out of scope: audio tracks, B-frames / composition offsets, H.265, a trailing moov, sidx / mfra,
+ * encryption. */
+typedef struct edgpu_mp4_config {    /* 0 in a field: the default */
+    uint64_t time_offset;            /* added to every dts, 90 kHz */
+    uint32_t max_samples;            /* per fragment; 0: no limit */
+    uint32_t default_duration;       /* 3600 */
+    uint32_t flags;                  /* none defined */
+    uint32_t _pad;
+} edgpu_mp4_config;
+typedef struct edgpu_mp4_state {     /* per stream, caller-held, zero to start */
+    uint64_t ext_ts;                 /* extended RTP timestamp of the last unit muxed */
+    uint64_t origin;                 /* ext of the first unit ever */
+    uint32_t sequence;               /* fragments emitted so far */
+    uint32_t last_step;              /* the last strictly positive sample step */
+    uint32_t started, _pad;
+} edgpu_mp4_state;
+typedef struct edgpu_mp4_sample {    /* one per input unit, same index */
+    uint64_t offset;                 /* of its bytes in `out` */
+    uint64_t dts;
+    uint32_t bytes, duration;
+    uint32_t flags;                  /* the tap unit's, | EDGPU_TAP_DAMAGED without a leading start code */
+    uint32_t fragment;               /* index of its fragment row; 0xFFFFFFFF: no sample */
+} edgpu_mp4_sample;
+typedef struct edgpu_mp4_frag {
+    uint64_t offset;                 /* of its moof in `out` */
+    uint64_t tfdt;
+    uint64_t duration;               /* sum of its samples' durations */
+    uint32_t bytes;                  /* moof + mdat */
+    uint32_t sequence;
+    uint32_t unit_first;             /* unit index of its first sample */
+    uint32_t samples;
+    uint32_t flags;
+    uint32_t stream;
+} edgpu_mp4_frag;
+typedef struct edgpu_mp4_result { uint64_t bytes; uint32_t units, frags, streams, _pad; } edgpu_mp4_result;
+/* Muxes on the context stream and syncs.  Pointer kinds, the host arrays and the index checks are
+ * those of edgpu_ts_mux; `samples` has n_units rows, `frags` frag_cap rows.  When out_cap or
+ * frag_cap is too small the call returns EDGPU_OUT_OVERFLOW, `result` holds the bytes, sample rows
+ * and fragment rows needed, and no byte of `out`, no row and no state is written: a retry with room
+ * gives what a first call would have given.  No byte outside a stream's run is written. */
+int  edgpu_mp4_mux(edgpu_ctx* ctx, const edgpu_mp4_config* cfg /* NULL: defaults */,
+                   const void* es, uint64_t es_bytes, int es_kind,
+                   const edgpu_tap_unit* units, uint32_t n_units,
+                   const edgpu_tap_stream* streams, uint32_t n_streams,
+                   edgpu_mp4_state* states /* n_streams, in/out */,
+                   void* out, uint64_t out_cap, int out_kind,
+                   edgpu_mp4_sample* samples /* n_units */,
+                   edgpu_mp4_frag* frags, uint32_t frag_cap, edgpu_mp4_result* result);
+/* The initialisation segment the fragments need: ftyp + moov (mvhd; one video trak with tkhd, mdia /
+ * mdhd / hdlr 'vide' / minf / vmhd / dinf / stbl; an avc1 sample entry with avcC; empty stts, stsc,
+ * stsz, stco; mvex / trex for track 1).  Host only: no context, nothing is launched.  `sps` and
+ * `pps` are one NAL each without start code (nal_unit_type 7 and 8, else EDGPU_BAD_ARGUMENT).
+ * avcC: version 1, profile / compatibility / level from SPS bytes 1..3, 4-byte lengths, the SPS, the
+ * PPS and, for profile_idc 100, 110, 122 and 144, chroma_format_idc and the bit depths.  Width and
+ * height (tkhd, sample entry) come from parsing the SPS (H.264 7.3.2.1.1: emulation prevention
+ * removed, scaling lists skipped, frame_mbs_only_flag, cropping in crop units); an SPS that does not
+ * parse is EDGPU_BAD_ARGUMENT.  timescale 0 means 90000.  *out_len receives the size; when `cap` is
+ * smaller the call returns EDGPU_OUT_OVERFLOW and writes nothing else. */
+int  edgpu_mp4_init(const uint8_t* sps, uint32_t sps_len, const uint8_t* pps, uint32_t pps_len, uint32_t timescale,
+                    uint8_t* out, uint64_t cap, uint64_t* out_len);
+
 /* Per-launch device durations (ms, HIP events on the ctx stream) recorded since the last
  * call, oldest first, for `which` = 0 fan-out copy kernel, 1 whole fan-out tick (plan +
  * copy), 2 ingest (with the keyframe index it carries), 3 keyframe index (no entries since the
  * index runs inside the ingest kernel), 4 the stream-statistics kernel, 5 a tap drain's kernels,
- * 6 a transport-stream mux's kernels (4, 5 and 6 recorded only at EDGPU_TIMING_ALL).  Up to 256 launches are kept; the history is
+ * 6 a transport-stream mux's kernels, 7 a fragmented-MP4 mux's kernels (4 to 7 recorded only at
+ * EDGPU_TIMING_ALL).  Up to 256 launches are kept; the history is
  * cleared after reading.  Syncs. */
 int  edgpu_kernel_times(edgpu_ctx* ctx, int which, float* out_ms, uint32_t max_n, uint32_t* out_n);
 

@@ -6,6 +6,13 @@ sessions of one H.264 track plus audio, --seconds long), taps every H.264 track,
 tick and writes <session>_<track>_<n>.h264 (Annex-B) under --out with index.json, the units of
 every file.  A file starts at the first KEY unit and a new file is cut at the first KEY unit
 --segment seconds after the file began: the reference recorder's rule (its segment is 300 s).
+
+--mp4 records fragmented MP4 instead (Context.tap_drain_mp4, easydarwin_amd/mp4.py): the units are
+muxed into moof + mdat fragments on the GPU and <session>_<track>_<n>.mp4 holds the initialisation
+segment and then the fragments, cut by the same rule.  A stream whose SPS does not parse (the
+synthetic push and the test traces carry random bytes in their parameter sets) gets the
+initialisation segment of a stand-in 640x480 Baseline SPS, so that its file still opens; the report
+counts them in "stand_in_init".
 """
 import argparse
 import json
@@ -54,6 +61,28 @@ class Recorder:
             json.dump({"files": self.files, "drained_units": self.drained_units}, f)
 
 
+# 640x480 Baseline, level 3.0, and a PPS: what StandInInit uses where a stream's own SPS does not parse
+STAND_IN_SPS = bytes([0x67, 0x42, 0x00, 0x1E, 0xF4, 0x05, 0x01, 0xEC, 0x80])
+STAND_IN_PPS = bytes([0x68, 0xCE, 0x3C, 0x80])
+
+
+class StandInInit:
+    """The `init` callable of mp4.Recorder / hls.Fmp4Segmenter: edgpu.mp4_init, with the stand-in
+    parameter sets where it refuses the stream's own."""
+
+    def __init__(self):
+        self.count = 0
+
+    def __call__(self, sps, pps):
+        try:
+            return edgpu.mp4_init(sps, pps)
+        except edgpu.EdgpuError as e:
+            if e.code != edgpu.BAD_ARGUMENT:
+                raise
+            self.count += 1
+            return edgpu.mp4_init(STAND_IN_SPS, STAND_IN_PPS)
+
+
 def synthetic(nsessions, seconds):
     tracks = [TrackSpec("video", "H264/90000", 96, bitrate=1_000_000, gop=30, idr_bytes=20_000),
               TrackSpec("audio", "PCMA/8000", 8)]
@@ -81,10 +110,17 @@ def main():
     ap.add_argument("--tick-ms", type=int, default=100)
     ap.add_argument("--segment", type=float, default=300.0, help="seconds per file")
     ap.add_argument("--out", required=True)
+    ap.add_argument("--mp4", action="store_true", help="record fragmented MP4 instead of Annex-B")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     sdps, pushes = from_trace(a.trace) if a.trace else synthetic(a.sessions, a.seconds)
-    rec = Recorder(a.out, int(a.segment * 1000))
+    if a.mp4:
+        from easydarwin_amd import mp4
+        init = StandInInit()
+        rec = mp4.Recorder(a.out, a.segment, init)
+    else:
+        rec = Recorder(a.out, int(a.segment * 1000))
+    units = 0
     with edgpu.Context(max_batch_packets=1 << 15, max_batch_bytes=32 << 20, out_arena_bytes=32 << 20,
                        max_out_packets=1 << 16) as ctx:
         sess = []
@@ -109,9 +145,18 @@ def main():
             if batch:
                 ctx.ingest_host(*edgpu.build_batch(batch))
                 ctx.keyframe_index()
-            rec.take(*ctx.tap_drain(flush=tick + a.tick_ms > end))
+            if a.mp4:
+                data, samples, frags, rows, streams = ctx.tap_drain_mp4(flush=tick + a.tick_ms > end)
+                units += len(rows)
+                rec.push(data, samples, frags, streams)
+            else:
+                rec.take(*ctx.tap_drain(flush=tick + a.tick_ms > end))
     rec.close()
-    print(json.dumps({"files": len(rec.files), "units": rec.drained_units}))
+    if a.mp4:
+        print(json.dumps({"files": sum(len(v["files"]) for v in rec.summary().values()), "units": units,
+                          "streams": rec.summary(), "stand_in_init": init.count}))
+    else:
+        print(json.dumps({"files": len(rec.files), "units": rec.drained_units}))
 
 
 if __name__ == "__main__":
