@@ -30,6 +30,7 @@
 #include "edgpu_device.h"
 #include "edgpu_params.h"
 #include "edgpu_bytes.h"
+#include "edgpu_wave.h"
 
 namespace edgpu {
 
@@ -165,12 +166,7 @@ __device__ __forceinline__ uint32_t dollar_mask(u32x4 w) {
             if (b + 16 > hi) mask &= (1u << (uint32_t)(hi - b)) - 1u;
         }
         const uint32_t cnt = (uint32_t)__popc(mask);
-        uint32_t incl = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += y;
-        }
+        const uint32_t incl = wave_incl(cnt, (uint32_t)lane);
         uint32_t idx = n + incl - cnt;
         while (mask) {
             const int i = __ffs(mask) - 1;
@@ -221,12 +217,7 @@ struct CandWin {
             if (b + 16 > w.hi) mask &= (1u << (uint32_t)(w.hi - b)) - 1u;
         }
         const uint32_t cnt = (uint32_t)__popc(mask);
-        uint32_t incl = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += y;
-        }
+        const uint32_t incl = wave_incl(cnt, (uint32_t)lane);
         uint32_t idx = n + incl - cnt;
         while (mask) {
             const int i = __ffs(mask) - 1;
@@ -246,29 +237,6 @@ struct CandWin {
         blk[round] = u32x4{0u, 0u, 0u, 0u};
         if (!w.none && !w.first && b < w.hi) blk[round] = *reinterpret_cast<const u32x4*>(b);
     }
-}
-
-template <typename T>
-__device__ __forceinline__ T block_exclusive_scan256(T v, T* scratch, T& total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    T x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        T y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) scratch[wid] = x;
-    __syncthreads();
-    T base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        T t = scratch[w];
-        if (w < wid) base += t;
-        tot += t;
-    }
-    __syncthreads();
-    total = tot;
-    return base + x - v;
 }
 
 }  // namespace
@@ -479,7 +447,7 @@ __global__ __launch_bounds__(256) void k_tcp_resolve(TcpParams P) {
             if (terminal) { s_stop_code = code; s_stop = start + ex; }
         }
         uint32_t tnf;
-        const uint32_t pnf = block_exclusive_scan256<uint32_t>(nf, scan32, tnf);
+        const uint32_t pnf = block_exclusive_scan<uint32_t>(nf, scan32, tnf);
         if ((uint32_t)tid < np) {
             TcpChunkRes R;
             R.entry = nf ? ent : kTcpNone;
@@ -628,12 +596,7 @@ __global__ __launch_bounds__(kScanThreads) void k_tcp_scan(TcpParams P) {
     const uint32_t g0 = tid * per, g1 = min(g0 + per, P.ngroups);
     uint32_t mine = 0;
     for (uint32_t g = g0; g < g1; g++) mine += P.groups[g].nframes;
-    uint32_t x = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
+    const uint32_t x = wave_incl(mine, (uint32_t)lane);
     if (lane == 63) s_w[wid] = x;
     __syncthreads();
     uint32_t base = 0, fb = 0;

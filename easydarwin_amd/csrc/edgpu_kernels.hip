@@ -25,6 +25,8 @@
 #include "edgpu_device.h"
 #include "edgpu_params.h"
 #include "edgpu_bytes.h"
+#include "edgpu_wave.h"
+#include "edgpu_rings.h"
 
 namespace edgpu {
 
@@ -87,73 +89,6 @@ __device__ __forceinline__ uint32_t packet_ssrc(const uint8_t* p, uint32_t len, 
     if (rtcp) return be32(p + 4);
     if (len < 12) return 0;
     return be32(p + 8);
-}
-
-// Inclusive scan of a 64-bit value across the wave, in registers: DPP row shifts (1, 2, 4, 8)
-// give each row of 16 lanes its own prefix, then every lane adds the totals of the rows before its
-// own (lanes 15, 31, 47, read as scalars).  Call with every lane active.
-template <int CTRL>
-__device__ __forceinline__ uint64_t dpp_u64(uint64_t x) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)x, CTRL, 0xF, 0xF, true);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(x >> 32), CTRL, 0xF, 0xF, true);
-    return (uint64_t)hi << 32 | lo;
-}
-__device__ __forceinline__ uint64_t readlane_u64(uint64_t x, int l) {
-    return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), l) << 32 |
-           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, l);
-}
-__device__ __forceinline__ uint64_t wave_inclusive_scan_u64(uint64_t x) {
-    x += dpp_u64<0x111>(x);                 // row_shr:1 (a row's first lanes read 0)
-    x += dpp_u64<0x112>(x);                 // row_shr:2
-    x += dpp_u64<0x114>(x);                 // row_shr:4
-    x += dpp_u64<0x118>(x);                 // row_shr:8
-    const uint64_t r0 = readlane_u64(x, 15), r1 = readlane_u64(x, 31), r2 = readlane_u64(x, 47);
-    const int row = (threadIdx.x & 63) >> 4;
-    return x + (row >= 1 ? r0 : 0ull) + (row >= 2 ? r1 : 0ull) + (row >= 3 ? r2 : 0ull);
-}
-
-// Exclusive scan over a workgroup of NW waves of 64 (256 threads by default).  `scratch` holds
-// NW entries.
-template <typename T, int NW = 4>
-__device__ __forceinline__ T block_exclusive_scan(T v, T* scratch, T& total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    T x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        T y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) scratch[wid] = x;
-    __syncthreads();
-    T base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < NW; w++) {
-        T t = scratch[w];
-        if (w < wid) base += t;
-        tot += t;
-    }
-    __syncthreads();
-    total = tot;
-    return base + x - v;
-}
-
-// Reduction over a workgroup of NW waves of 64 (every thread gets the result); `scratch` holds
-// NW entries and may be reused right after.
-struct OpSum { template <typename T> __device__ T operator()(T a, T b) const { return a + b; } };
-struct OpMax { template <typename T> __device__ T operator()(T a, T b) const { return a > b ? a : b; } };
-struct OpMin { template <typename T> __device__ T operator()(T a, T b) const { return a < b ? a : b; } };
-template <typename T, typename Op, int NW = 4>
-__device__ __forceinline__ T block_reduce(T v, T* scratch) {
-    const Op op;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = op(v, (T)__shfl_xor(v, o, 64));
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    T r = scratch[0];
-#pragma unroll
-    for (int w = 1; w < NW; w++) r = op(r, scratch[w]);
-    __syncthreads();
-    return r;
 }
 
 // =========================================================================================
@@ -1070,24 +1005,6 @@ __global__ __launch_bounds__(256) void k_plan_subs(PlanParams P) {
     }
 }
 
-// Inclusive scan over a workgroup of up to 1024 threads: shuffles inside each wave, then the
-// wave totals (wsum, one per wave) through LDS.  Every thread of the block must call it.
-template <typename T>
-__device__ __forceinline__ T wave_block_inclusive_scan(T v, T* wsum) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T y = __shfl_up(v, o, 64);
-        if (lane >= o) v += y;
-    }
-    if (lane == 63) wsum[w] = v;
-    __syncthreads();
-    T base = 0;
-    for (int i = 0; i < w; i++) base += wsum[i];
-    __syncthreads();                                  // wsum may be reused by the next call
-    return v + base;
-}
-
 // K3: per sub-stream -- final arena / descriptor offsets and the public sub-stream table;
 // per sender -- work items.  Each block adds up the K2 partials of the blocks before it (a few
 // hundred at most), so the offsets need no separate scan launch; block 0 adds up all of them
@@ -1356,8 +1273,6 @@ __global__ void k_blocked(BlockedParams P) {
 // =========================================================================================
 // Fan-out
 // =========================================================================================
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // -----------------------------------------------------------------------------------------
 // k_fanout4: LDS-staged, line-aligned write-many.  A work item's chunk is loaded from HBM into
@@ -1809,14 +1724,10 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, THREADS))) void k_fanou
 // the replica receives exactly what it would receive joining the owner.
 // =========================================================================================
 
+// The oldest index still intact in both of the sender's rings
 __device__ uint64_t sender_tail(const SenderDev& D) {
-    const PktMeta* meta = reinterpret_cast<const PktMeta*>(D.meta);
-    const uint64_t head = D.head, pk_cap = (uint64_t)D.pk_mask + 1;
-    const uint64_t byte_cap = ((uint64_t)D.word_mask + 1) * 16, vend = max(D.vbyte_end, D.vclob);
-    uint64_t lo = head > pk_cap ? head - pk_cap : 0;
-    lo = max(lo, D.floor);
-    return lower_bound_meta(meta, D.pk_mask, lo, head,
-                            [&](const PktMeta& m) { return vend - m.vbyte <= byte_cap; });
+    const Rings R{reinterpret_cast<const u32x4*>(D.meta), reinterpret_cast<const u32x4*>(D.ring), D.pk_mask, D.word_mask};
+    return intact_from(D, R, 0, D.head);
 }
 
 // RTP-Info PLAY (HaveStreamBuffers, QTSSReflectorModule.cpp:1804-1865): per track,

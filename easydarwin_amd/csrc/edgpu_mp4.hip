@@ -36,44 +36,13 @@
 #include "edgpu_device.h"
 #include "edgpu_params.h"
 #include "edgpu_bytes.h"
+#include "edgpu_wave.h"
 
 namespace edgpu {
 namespace {
 
 constexpr uint32_t kMp4PlaceThreads = 256;
 constexpr uint32_t kChunkBytes = kMp4ChunkWords * 32;
-
-__device__ __forceinline__ uint32_t m_uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t m_uni64(uint64_t v) { return ((uint64_t)m_uni((uint32_t)(v >> 32)) << 32) | m_uni((uint32_t)v); }
-__device__ __forceinline__ uint32_t m_lane(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
-__device__ __forceinline__ uint64_t m_lane64(uint64_t v, uint32_t l) { return ((uint64_t)m_lane((uint32_t)(v >> 32), l) << 32) | m_lane((uint32_t)v, l); }
-__device__ __forceinline__ uint64_t m_shfl64(uint64_t v, uint32_t l) {
-    return ((uint64_t)(uint32_t)__shfl((int)(v >> 32), (int)l, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)v, (int)l, 64);
-}
-__device__ __forceinline__ uint32_t m_incl(uint32_t v, uint32_t lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(v, o, 64);
-        if (lane >= (uint32_t)o) v += u;
-    }
-    return v;
-}
-__device__ __forceinline__ uint32_t m_inclmax(uint32_t v, uint32_t lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(v, o, 64);
-        if (lane >= (uint32_t)o) v = v > u ? v : u;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t m_incl64(uint64_t v, uint32_t lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t lo = __shfl_up((uint32_t)v, o, 64), hi = __shfl_up((uint32_t)(v >> 32), o, 64);
-        if (lane >= (uint32_t)o) v += ((uint64_t)hi << 32) | lo;
-    }
-    return v;
-}
 
 // Bits [lo, lo + 32) of the bitmap
 __device__ __forceinline__ uint32_t m_bits(const Mp4Params& P, uint64_t lo) {
@@ -142,7 +111,7 @@ __global__ __launch_bounds__(256) void k_mp4_resolve(Mp4Params P) {
             const uint64_t b2 = __ballot(v != kMp4None);
             if (b2) {
                 const uint32_t l2 = (uint32_t)__builtin_ctzll(b2);
-                far = (cc + l2) * kChunkBytes + m_lane(v, l2);
+                far = (cc + l2) * kChunkBytes + lane_of(v, l2);
                 break;
             }
         }
@@ -163,15 +132,15 @@ __global__ __launch_bounds__(64) void k_mp4_plan(Mp4Params P) {
     const uint32_t s = blockIdx.x;
     if (s >= P.n_streams) return;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t first = m_uni(P.ranges[s].first), count = m_uni(P.ranges[s].count), slot0 = m_uni(P.ranges[s].slot);
+    const uint32_t first = uni(P.ranges[s].first), count = uni(P.ranges[s].count), slot0 = uni(P.ranges[s].slot);
     const edgpu_mp4_state st = P.states[s];
-    const uint32_t started = m_uni(st.started);
-    uint64_t c_ext = m_uni64(started ? st.ext_ts : 0ull);
-    uint64_t origin = m_uni64(st.origin);
-    if (!started && count) origin = m_uni(P.units[first].rtp_ts);
+    const uint32_t started = uni(st.started);
+    uint64_t c_ext = uni(started ? st.ext_ts : (uint64_t)0);
+    uint64_t origin = uni(st.origin);
+    if (!started && count) origin = uni(P.units[first].rtp_ts);
     const uint32_t maxs = P.max_samples;
     uint32_t c_rank = 0, c_bytes = 0, c_nfrag = 0, c_seg1 = 0, c_fragb1 = 0, c_or = 0;
-    uint32_t c_prev_unit = 0, c_has_prev = 0, c_step = m_uni(st.last_step);
+    uint32_t c_prev_unit = 0, c_has_prev = 0, c_step = uni(st.last_step);
     uint64_t c_dsum = 0, c_prev_ext = 0;
     for (uint32_t base = 0; base < count; base += 64) {
         const uint32_t i = base + lane;
@@ -190,22 +159,22 @@ __global__ __launch_bounds__(64) void k_mp4_plan(Mp4Params P) {
         if (lane == 0) prev_ts = (uint32_t)c_ext;
         uint64_t d = valid ? (uint64_t)(int64_t)(int32_t)(ts - prev_ts) : 0ull;
         if (valid && i == 0 && !started) d = ts;
-        const uint64_t in_d = m_incl64(d, lane);
+        const uint64_t in_d = wave_incl(d, lane);
         const uint64_t ext = c_ext + in_d;
         const uint64_t dts = ext - origin + P.time_offset;
         // ranks, bytes, fragment starts
-        const uint32_t in_has = m_incl(has, lane), in_b = m_incl(bytes, lane);
+        const uint32_t in_has = wave_incl(has, lane), in_b = wave_incl(bytes, lane);
         const uint32_t r = c_rank + in_has - has;
         const uint32_t bex = c_bytes + in_b - bytes;
         const bool key = hasb && (flags & EDGPU_TAP_KEY);
         const bool segstart = hasb && (key || r == 0);
-        const uint32_t in_seg = m_inclmax(segstart ? r + 1 : 0u, lane);
+        const uint32_t in_seg = wave_incl_max(segstart ? r + 1 : 0u, lane);
         const uint32_t seg1 = in_seg > c_seg1 ? in_seg : c_seg1;          // rank + 1 of the last key (or first) sample
         const uint32_t pos = hasb ? r - (seg1 - 1) : 0u;
         const bool fragstart = hasb && (maxs ? pos % maxs == 0 : pos == 0);
-        const uint32_t in_fs = m_incl(fragstart ? 1u : 0u, lane);
+        const uint32_t in_fs = wave_incl(fragstart ? 1u : 0u, lane);
         const uint32_t fi = c_nfrag + in_fs - 1;                           // of a sample: its fragment, within the stream
-        const uint32_t in_fb = m_inclmax(fragstart ? bex + 1 : 0u, lane);
+        const uint32_t in_fb = wave_incl_max(fragstart ? bex + 1 : 0u, lane);
         const uint32_t fragb1 = in_fb > c_fragb1 ? in_fb : c_fragb1;
         // OR of the flags within the fragment so far: a segmented scan, heads at the fragment starts
         uint32_t ov = hasb ? flags : 0u, of = fragstart ? 1u : 0u;
@@ -218,9 +187,9 @@ __global__ __launch_bounds__(64) void k_mp4_plan(Mp4Params P) {
         uint32_t prev_or = __shfl_up(ov, 1, 64);
         if (lane == 0) prev_or = c_or;
         // the sample before this one: its duration is known here
-        uint32_t pl = __shfl_up(m_inclmax(hasb ? lane + 1 : 0u, lane), 1, 64);
+        uint32_t pl = __shfl_up(wave_incl_max(hasb ? lane + 1 : 0u, lane), 1, 64);
         if (lane == 0) pl = 0;
-        const uint64_t pext_w = m_shfl64(ext, pl ? pl - 1 : 0u);
+        const uint64_t pext_w = shfl64(ext, pl ? pl - 1 : 0u);
         const bool hp = hasb && (pl || c_has_prev);
         const uint64_t pext = pl ? pext_w : c_prev_ext;
         const uint32_t punit = pl ? first + base + pl - 1 : c_prev_unit;
@@ -232,7 +201,7 @@ __global__ __launch_bounds__(64) void k_mp4_plan(Mp4Params P) {
             dp = diff <= 0 ? 0u : diff > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)diff;
             P.recs[punit].duration = dp;
         }
-        const uint64_t in_dp = m_incl64(dp, lane);
+        const uint64_t in_dp = wave_incl((uint64_t)dp, lane);
         if (valid) {
             Mp4Rec* r_ = &P.recs[first + i];                // every field but `duration`: the next sample's lane writes that
             r_->dts = dts;
@@ -254,20 +223,20 @@ __global__ __launch_bounds__(64) void k_mp4_plan(Mp4Params P) {
             P.frecs[slot0 + fi] = f;
         }
         // carries
-        c_ext += m_lane64(in_d, 63);
-        c_rank += m_lane(in_has, 63);
-        c_bytes += m_lane(in_b, 63);
-        c_nfrag += m_lane(in_fs, 63);
-        c_dsum += m_lane64(in_dp, 63);
-        c_seg1 = m_lane(seg1, 63);
-        c_fragb1 = m_lane(fragb1, 63);
-        c_or = m_lane(ov, 63);
+        c_ext += lane_of(in_d, 63);
+        c_rank += lane_of(in_has, 63);
+        c_bytes += lane_of(in_b, 63);
+        c_nfrag += lane_of(in_fs, 63);
+        c_dsum += lane_of(in_dp, 63);
+        c_seg1 = lane_of(seg1, 63);
+        c_fragb1 = lane_of(fragb1, 63);
+        c_or = lane_of(ov, 63);
         const uint64_t pb = __ballot(positive);
-        if (pb) c_step = m_lane(dp, 63u - (uint32_t)__builtin_clzll(pb));
+        if (pb) c_step = lane_of(dp, 63u - (uint32_t)__builtin_clzll(pb));
         const uint64_t hb = __ballot(hasb);
         if (hb) {
             const uint32_t hl = 63u - (uint32_t)__builtin_clzll(hb);
-            c_prev_ext = m_lane64(ext, hl);
+            c_prev_ext = lane_of(ext, hl);
             c_prev_unit = first + base + hl;
             c_has_prev = 1;
         }
@@ -305,38 +274,28 @@ __global__ __launch_bounds__(64) void k_mp4_plan(Mp4Params P) {
 }
 
 __global__ __launch_bounds__(256) void k_mp4_place(Mp4Params P) {
-    __shared__ uint64_t lb[kMp4PlaceThreads];
-    __shared__ uint64_t lf[kMp4PlaceThreads];
-    __shared__ uint64_t total;
+    __shared__ uint64_t scratch[kMp4PlaceThreads / 64];
     const uint32_t t = threadIdx.x;
     uint64_t cb = 0, cf = 0;
-    if (t == 0) total = 0;
     for (uint32_t b = 0; b < P.n_streams; b += kMp4PlaceThreads) {
         const uint32_t i = b + t;
         const uint64_t bytes = i < P.n_streams ? P.srecs[i].bytes : 0ull;
         const uint64_t vb = (bytes + 15) & ~15ull;
         const uint64_t vf = i < P.n_streams ? P.srecs[i].nfrags : 0ull;
-        __syncthreads();
-        lb[t] = vb; lf[t] = vf;
-        __syncthreads();
-        for (uint32_t o = 1; o < kMp4PlaceThreads; o <<= 1) {
-            const uint64_t ub = t >= o ? lb[t - o] : 0ull, uf = t >= o ? lf[t - o] : 0ull;
-            __syncthreads();
-            lb[t] += ub; lf[t] += uf;
-            __syncthreads();
-        }
+        uint64_t tb, tf;
+        const uint64_t base = cb + block_exclusive_scan<uint64_t>(vb, scratch, tb);
+        const uint64_t fbase = cf + block_exclusive_scan<uint64_t>(vf, scratch, tf);
         if (i < P.n_streams) {
-            const uint64_t base = cb + lb[t] - vb;
-            const uint64_t fbase = cf + lf[t] - vf;
             P.srecs[i].base = base;
             P.srecs[i].fbase = fbase > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)fbase;
-            if (i == P.n_streams - 1) total = base + bytes;
         }
-        cb += lb[kMp4PlaceThreads - 1];
-        cf += lf[kMp4PlaceThreads - 1];
+        cb += tb;
+        cf += tf;
     }
-    __syncthreads();
     if (t == 0) {
+        // the last run is not padded: its base + bytes is the sum of every run less the last one's padding
+        const uint64_t last = P.n_streams ? P.srecs[P.n_streams - 1].bytes : 0ull;
+        const uint64_t total = cb - (((last + 15) & ~15ull) - last);
         Mp4Place pl;
         pl.bytes = total;
         pl.frags = cf > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cf;

@@ -23,6 +23,8 @@
 #include "edgpu_device.h"
 #include "edgpu_params.h"
 #include "edgpu_bytes.h"
+#include "edgpu_wave.h"
+#include "edgpu_rings.h"
 
 namespace edgpu {
 namespace {
@@ -34,67 +36,6 @@ constexpr uint32_t kRtpHeader = 12;             // a packet shorter than this ha
 constexpr uint32_t kSrBytes = 28;               // RTCP header + SSRC + sender info
 constexpr uint32_t kRtcpSr = 200;
 constexpr int64_t kBitRateAvgIntervalMs = 30000;    // ReflectorStream::kBitRateAvgIntervalInMilSecs
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni(uint64_t v) { return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v); }
-__device__ __forceinline__ uint32_t lane_of(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// One sender's rings as the walk reads them.
-struct Rings {
-    const u32x4* meta;          // PktMeta as two 16-B words
-    const u32x4* ring;
-    uint32_t pk_mask, word_mask;
-};
-
-// The oldest index >= `from` still intact in both rings (sender_tail's test): the meta ring holds
-// the last pk_mask + 1 entries, the byte ring the last (word_mask + 1) * 16 bytes written.
-__device__ uint64_t intact_from(const SenderDev& D, const Rings& R, uint64_t from, uint64_t head) {
-    const PktMeta* meta = reinterpret_cast<const PktMeta*>(R.meta);
-    const uint64_t pk_cap = (uint64_t)R.pk_mask + 1, byte_cap = ((uint64_t)R.word_mask + 1) * 16;
-    const uint64_t vend = max(D.vbyte_end, D.vclob);
-    uint64_t lo = max(from, (uint64_t)D.floor);
-    if (lo >= head) return head;
-    if (head - lo > pk_cap) lo = head - pk_cap;
-    if (vend - meta[lo & R.pk_mask].vbyte <= byte_cap) return lo;      // nothing lost: the usual case
-    uint64_t hi = head;
-    lo++;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (vend - meta[mid & R.pk_mask].vbyte <= byte_cap) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-
-// Lane's PktMeta of queue index i (zero, i.e. an empty packet, when i is past the head)
-__device__ __forceinline__ void load_meta(const Rings& R, uint64_t i, uint64_t head, u32x4& m0, u32x4& m1) {
-    m0 = m1 = u32x4{0u, 0u, 0u, 0u};
-    if (i < head) {
-        const u32x4* p = R.meta + 2 * (size_t)(i & R.pk_mask);
-        m0 = p[0];
-        m1 = p[1];
-    }
-}
-__device__ __forceinline__ uint32_t meta_len(const u32x4& m1) { return m1.z & 0xFFFFu; }
-// Word `k` of the packet's slot, when the packet has at least `need` bytes
-__device__ __forceinline__ u32x4 load_word(const Rings& R, const u32x4& m0, const u32x4& m1, uint32_t need, uint32_t k) {
-    u32x4 w = u32x4{0u, 0u, 0u, 0u};
-    if (meta_len(m1) >= need) {
-        const uint64_t vbyte = (uint64_t)m0.x | ((uint64_t)m0.y << 32);
-        w = R.ring[(size_t)(((vbyte >> 4) + k) & R.word_mask)];
-    }
-    return w;
-}
 
 }  // namespace
 

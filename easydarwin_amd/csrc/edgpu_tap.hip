@@ -32,6 +32,8 @@
 #include "edgpu_device.h"
 #include "edgpu_params.h"
 #include "edgpu_bytes.h"
+#include "edgpu_wave.h"
+#include "edgpu_rings.h"
 
 namespace edgpu {
 namespace {
@@ -39,54 +41,8 @@ namespace {
 constexpr uint32_t kNoChain = 0xFFu;
 constexpr uint32_t kPlaceThreads = 256;
 
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni(uint64_t v) { return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v); }
-__device__ __forceinline__ uint32_t lane_of(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
 __device__ __forceinline__ uint32_t bit_of(unsigned long long m, uint32_t l) { return (uint32_t)((m >> l) & 1ull); }
 __device__ __forceinline__ uint32_t top_bit(unsigned long long m) { return 63u - (uint32_t)__clzll((long long)m); }
-
-__device__ __forceinline__ uint32_t wave_incl(uint32_t v, uint32_t lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(v, o, 64);
-        if (lane >= (uint32_t)o) v += u;
-    }
-    return v;
-}
-
-struct Rings {
-    const u32x4* meta;          // PktMeta as two 16-B words
-    const u32x4* ring;
-    uint32_t pk_mask, word_mask;
-};
-
-// The oldest index >= `from` still intact in both rings (as k_stream_stats finds it).
-__device__ uint64_t intact_from(const SenderDev& D, const Rings& R, uint64_t from, uint64_t head) {
-    const PktMeta* meta = reinterpret_cast<const PktMeta*>(R.meta);
-    const uint64_t pk_cap = (uint64_t)R.pk_mask + 1, byte_cap = ((uint64_t)R.word_mask + 1) * 16;
-    const uint64_t vend = max(D.vbyte_end, D.vclob);
-    uint64_t lo = max(from, (uint64_t)D.floor);
-    if (lo >= head) return head;
-    if (head - lo > pk_cap) lo = head - pk_cap;
-    if (vend - meta[lo & R.pk_mask].vbyte <= byte_cap) return lo;
-    uint64_t hi = head;
-    lo++;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (vend - meta[mid & R.pk_mask].vbyte <= byte_cap) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-
-// Byte `off` of the packet whose slot starts at virtual byte `vbyte` (the packet starts at slot byte 4)
-__device__ __forceinline__ uint32_t pkt_byte(const Rings& R, uint64_t vbyte, uint32_t off) {
-    const uint64_t mask = ((uint64_t)R.word_mask << 4) | 15u;
-    return reinterpret_cast<const uint8_t*>(R.ring)[(vbyte + 4 + off) & mask];
-}
-__device__ __forceinline__ uint32_t ring_byte(const u32x4* ring, uint32_t word_mask, uint64_t v) {
-    const uint64_t mask = ((uint64_t)word_mask << 4) | 15u;
-    return reinterpret_cast<const uint8_t*>(ring)[v & mask];
-}
 
 // Totals of a drain so far: entries, and what the good packets among them did
 struct Tally {
@@ -354,26 +310,8 @@ __global__ __launch_bounds__(64) void k_tap_scan(TapParams P) {
     }
 }
 
-// Exclusive sums over the workgroup's 256 values; `carry` (every thread's copy) moves on by their total.
-__device__ __forceinline__ uint64_t block_excl(uint64_t v, uint64_t* lds, uint64_t& carry) {
-    const uint32_t t = threadIdx.x;
-    __syncthreads();
-    lds[t] = v;
-    __syncthreads();
-    for (uint32_t o = 1; o < kPlaceThreads; o <<= 1) {
-        const uint64_t u = t >= o ? lds[t - o] : 0ull;
-        __syncthreads();
-        lds[t] += u;
-        __syncthreads();
-    }
-    const uint64_t incl = lds[t], total = lds[kPlaceThreads - 1];
-    const uint64_t r = carry + incl - v;
-    carry += total;
-    return r;
-}
-
 __global__ __launch_bounds__(256) void k_tap_place(TapParams P) {
-    __shared__ uint64_t lds[kPlaceThreads];
+    __shared__ uint64_t scratch[kPlaceThreads / 64];
     uint64_t c_bytes = 0, c_units = 0, c_items = 0, c_uitems = 0;
     uint32_t* items = P.items;
     uint32_t* uitems = P.items + P.ntaps + 1;
@@ -388,8 +326,12 @@ __global__ __launch_bounds__(256) void k_tap_place(TapParams P) {
             it = (T->d_nrec + kTapRound - 1) / kTapRound;
             ui = (T->d_nunits + kTapRound - 1) / kTapRound;
         }
-        const uint64_t o_by = block_excl(by, lds, c_bytes), o_un = block_excl(un, lds, c_units);
-        const uint64_t o_it = block_excl(it, lds, c_items), o_ui = block_excl(ui, lds, c_uitems);
+        uint64_t t_by, t_un, t_it, t_ui;                    // the block's totals; the carries are every thread's copy
+        const uint64_t o_by = c_bytes + block_exclusive_scan<uint64_t>(by, scratch, t_by);
+        const uint64_t o_un = c_units + block_exclusive_scan<uint64_t>(un, scratch, t_un);
+        const uint64_t o_it = c_items + block_exclusive_scan<uint64_t>(it, scratch, t_it);
+        const uint64_t o_ui = c_uitems + block_exclusive_scan<uint64_t>(ui, scratch, t_ui);
+        c_bytes += t_by; c_units += t_un; c_items += t_it; c_uitems += t_ui;
         if (T) {
             T->p_offset = o_by;
             T->p_unit_first = (uint32_t)o_un;
