@@ -287,9 +287,10 @@ struct edgpu_ctx {
     // (ring 5, a tap drain's kernels: by the first edgpu_tap_enable)
     // (ring 6, a transport-stream mux's kernels: by the first edgpu_ts_mux)
     // (ring 7, a fragmented-MP4 mux's kernels: by the first edgpu_mp4_mux)
-    hipEvent_t hist[8][kHist][2] = {};
-    uint32_t hist_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // pairs recorded (monotonic sequence numbers)
-    uint32_t hist_rd[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // pairs already returned by edgpu_kernel_times
+    // (ring 8, an FLV mux's kernels: by the first edgpu_flv_mux)
+    hipEvent_t hist[9][kHist][2] = {};
+    uint32_t hist_n[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // pairs recorded (monotonic sequence numbers)
+    uint32_t hist_rd[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // pairs already returned by edgpu_kernel_times
     // Borrowed end points.  A whole-tick entry (ring 1) ends at its copy kernel's end event
     // (ring 0 sequence number in tick_end[slot]); a keyframe entry (ring 3) starts at the end
     // event of the ingest it indexes (ring 2 sequence number in kf_from[slot]) when nothing ran
@@ -298,7 +299,7 @@ struct edgpu_ctx {
     static const uint32_t kOwnStart = 0xFFFFFFFFu;
     uint32_t tick_end[kHist] = {};
     uint32_t kf_from[kHist] = {};
-    uint32_t last_seq[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // each ring's newest complete pair (edgpu_last_timings)
+    uint32_t last_seq[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // each ring's newest complete pair (edgpu_last_timings)
     bool kf_share = false;                  // the last ingest's end event may start the keyframe entry
     uint64_t fanout_launches = 0;
     int64_t last_now = 0;               // clock of the last edgpu_fanout (backpressure reports)
@@ -364,6 +365,16 @@ struct edgpu_ctx {
     DevVec<edgpu_mp4_sample> d_mp4_rows;
     DevVec<edgpu_mp4_frag> d_mp4_frags;
     Mp4Place* d_mp4_place = nullptr;
+    // the FLV mux (edgpu_flv_mux): staging and work buffers only, allocated by the first call
+    DevVec<uint8_t> d_flv_es, d_flv_out;
+    DevVec<uint32_t> d_flv_bitmap, d_flv_chunks, d_flv_lens;
+    DevVec<edgpu_tap_unit> d_flv_units_in;
+    DevVec<FlvRange> d_flv_ranges;
+    DevVec<edgpu_flv_state> d_flv_states;   // 2 x n_streams: the caller's rows, the new rows
+    DevVec<FlvRec> d_flv_recs;
+    DevVec<FlvStreamRec> d_flv_srecs;
+    DevVec<edgpu_flv_tag> d_flv_rows;
+    FlvPlace* d_flv_place = nullptr;
     DevVec<SubDev> d_subs;
     DevVec<uint32_t> d_sub_index;
     DevVec<uint32_t> d_sub_range;
@@ -679,6 +690,10 @@ int edgpu_ctx_destroy(edgpu_ctx* x) {
     x->d_mp4_units_in.release(); x->d_mp4_ranges.release(); x->d_mp4_states.release(); x->d_mp4_recs.release();
     x->d_mp4_frecs.release(); x->d_mp4_srecs.release(); x->d_mp4_samps.release(); x->d_mp4_rows.release(); x->d_mp4_frags.release();
     if (x->d_mp4_place) (void)hipFree(x->d_mp4_place);
+    x->d_flv_es.release(); x->d_flv_out.release(); x->d_flv_bitmap.release(); x->d_flv_chunks.release(); x->d_flv_lens.release();
+    x->d_flv_units_in.release(); x->d_flv_ranges.release(); x->d_flv_states.release(); x->d_flv_recs.release();
+    x->d_flv_srecs.release(); x->d_flv_rows.release();
+    if (x->d_flv_place) (void)hipFree(x->d_flv_place);
     x->d_carry.release(); x->d_tcp_groups.release(); x->d_tcp_reads.release(); x->d_tcp_chunk_group.release();
     x->d_tcp_ncand.release(); x->d_tcp_cands.release(); x->d_tcp_links.release(); x->d_tcp_chunkres.release();
     x->d_tcp_results.release(); x->d_tcp_offs.release(); x->d_tcp_stage.release(); x->d_blocked.release();
@@ -2804,12 +2819,12 @@ int edgpu_mp4_mux(edgpu_ctx* x, const edgpu_mp4_config* cfg, const void* es, uin
     if (covered != n_units) HIP_CHECK(hipMemsetAsync(x->d_mp4_recs.ptr, 0, (size_t)n_units * sizeof(Mp4Rec), x->stream));
     HIP_CHECK(wsync(x, x->stream));             // `ranges` is on the stack
     Mp4Params p;
-    p.es = device_es ? (const uint8_t*)es : x->d_mp4_es.ptr;
-    p.es_bytes = es_bytes;
+    p.sc.es = device_es ? (const uint8_t*)es : x->d_mp4_es.ptr;
+    p.sc.es_bytes = es_bytes;
     p.units = x->d_mp4_units_in.ptr; p.ranges = x->d_mp4_ranges.ptr;
     p.states = x->d_mp4_states.ptr; p.new_states = x->d_mp4_states.ptr + n_streams;
-    p.bitmap = x->d_mp4_bitmap.ptr; p.chunk_first = x->d_mp4_chunks.ptr; p.lens = x->d_mp4_lens.ptr;
-    p.nwords = nwords; p.nchunks = nchunks;
+    p.sc.bitmap = x->d_mp4_bitmap.ptr; p.sc.chunk_first = x->d_mp4_chunks.ptr; p.sc.lens = x->d_mp4_lens.ptr;
+    p.sc.nwords = nwords; p.sc.nchunks = nchunks;
     p.recs = x->d_mp4_recs.ptr; p.frecs = x->d_mp4_frecs.ptr; p.srecs = x->d_mp4_srecs.ptr; p.samps = x->d_mp4_samps.ptr;
     p.place = x->d_mp4_place;
     p.out = device_out ? (uint8_t*)out : x->d_mp4_out.ptr;
@@ -2851,8 +2866,125 @@ int edgpu_mp4_mux(edgpu_ctx* x, const edgpu_mp4_config* cfg, const void* es, uin
     return EDGPU_OK;
 }
 
+// ---- FLV mux of tapped access units (edgpu_flv_mux; edgpu_flv.hip) ----
+int edgpu_flv_mux(edgpu_ctx* x, const edgpu_flv_config* cfg, const void* es, uint64_t es_bytes, int es_kind,
+                  const edgpu_tap_unit* units, uint32_t n_units, const edgpu_tap_stream* streams, uint32_t n_streams,
+                  edgpu_flv_state* states, void* out, uint64_t out_cap, int out_kind, edgpu_flv_tag* tags,
+                  edgpu_flv_result* result) {
+    if (!x || !result || (!es && es_bytes) || (!out && out_cap) || (!units && n_units) || (!tags && n_units) ||
+        (!streams && n_streams) || (!states && n_streams))
+        return fail(EDGPU_BAD_ARGUMENT, "bad argument");
+    for (int k : {es_kind, out_kind})
+        if (k != EDGPU_PTR_HOST && k != EDGPU_PTR_DEVICE && k != EDGPU_PTR_PINNED) return fail(EDGPU_BAD_ARGUMENT, "bad pointer kind");
+    const bool device_es = es_kind == EDGPU_PTR_DEVICE, device_out = out_kind == EDGPU_PTR_DEVICE;
+    if ((device_es && ((uintptr_t)es & 15)) || (device_out && ((uintptr_t)out & 15)))
+        return fail(EDGPU_BAD_ARGUMENT, "device `es` and `out` must be 16-B aligned");
+    edgpu_flv_config c;
+    memset(&c, 0, sizeof(c));
+    if (cfg) c = *cfg;
+    if (c.flags) return fail(EDGPU_BAD_ARGUMENT, "bad FLV configuration: no flags are defined");
+    // the rows the kernels index by: checked here, on the host
+    for (uint32_t i = 0; i < n_units; i++) {
+        if (units[i].stream >= n_streams) return fail(EDGPU_BAD_ARGUMENT, "a unit's stream index is out of range");
+        if (units[i].offset > es_bytes || units[i].bytes > es_bytes - units[i].offset)
+            return fail(EDGPU_BAD_ARGUMENT, "a unit reaches outside the ES bytes");
+        if (units[i].bytes > 0xFFFFFAu) return fail(EDGPU_BAD_ARGUMENT, "a unit of more than 0xFFFFFA bytes: an FLV tag's DataSize is 24 bits");
+    }
+    std::vector<FlvRange> ranges(n_streams);
+    uint64_t covered = 0, next = 0, most = 0;       // `most`: the bytes the output can need at the most
+    for (uint32_t s = 0; s < n_streams; s++) {
+        const uint64_t first = streams[s].unit_first, count = streams[s].unit_count;
+        if (first + count > n_units) return fail(EDGPU_BAD_ARGUMENT, "a stream's unit range reaches outside the units");
+        if (count) {
+            if (first < next) return fail(EDGPU_BAD_ARGUMENT, "the streams' unit ranges must ascend without overlap");
+            next = first + count;
+        }
+        uint64_t total = 0;
+        for (uint64_t i = first; i < first + count; i++) total += units[i].bytes;
+        if (total + 20 * count >= (1ull << 32))     // offsets within a run are 32-bit
+            return fail(EDGPU_BAD_ARGUMENT, "a stream's run could reach 2^32 bytes");
+        ranges[s] = FlvRange{(uint32_t)first, (uint32_t)count};
+        covered += count;
+        most += total + 20 * count + 16;
+    }
+    memset(result, 0, sizeof(*result));
+    result->units = n_units; result->streams = n_streams;
+    if (!n_streams) {
+        if (n_units) memset(tags, 0, (size_t)n_units * sizeof(edgpu_flv_tag));
+        return EDGPU_OK;
+    }
+    DEVICE_ENTER(x);
+    if (!x->hist[8][0][0])
+        for (auto& s : x->hist[8]) for (auto& e : s) HIP_CHECK(hipEventCreate(&e));
+    if (!x->d_flv_place && dmalloc(&x->d_flv_place, sizeof(FlvPlace)) != hipSuccess)
+        return fail(EDGPU_OUT_OF_MEMORY, "FLV mux staging");
+    const uint64_t nwords = (es_bytes + 31) / 32, nchunks = (nwords + kScodeChunkWords - 1) / kScodeChunkWords;
+    const size_t nu = std::max<uint32_t>(n_units, 1);
+    HIP_CHECK(x->d_flv_units_in.reserve(nu, x->stream));
+    HIP_CHECK(x->d_flv_recs.reserve(nu, x->stream));
+    HIP_CHECK(x->d_flv_rows.reserve(nu, x->stream));
+    HIP_CHECK(x->d_flv_ranges.reserve(n_streams, x->stream));
+    HIP_CHECK(x->d_flv_srecs.reserve(n_streams, x->stream));
+    HIP_CHECK(x->d_flv_states.reserve(2 * (size_t)n_streams, x->stream));
+    HIP_CHECK(x->d_flv_bitmap.reserve(nwords + 1, x->stream));
+    HIP_CHECK(x->d_flv_chunks.reserve(nchunks + 1, x->stream));
+    HIP_CHECK(x->d_flv_lens.reserve(es_bytes / 4 + 1, x->stream));
+    if (!device_es) HIP_CHECK(x->d_flv_es.reserve(es_bytes + 16, x->stream));
+    // staging for the most the units can need, so the verdict never depends on the staging
+    if (!device_out) HIP_CHECK(x->d_flv_out.reserve(std::max<uint64_t>(std::min<uint64_t>(out_cap, most), 16), x->stream));
+    if (n_units) HIP_CHECK(hipMemcpyAsync(x->d_flv_units_in.ptr, units, (size_t)n_units * sizeof(edgpu_tap_unit), hipMemcpyHostToDevice, x->stream));
+    HIP_CHECK(hipMemcpyAsync(x->d_flv_ranges.ptr, ranges.data(), (size_t)n_streams * sizeof(FlvRange), hipMemcpyHostToDevice, x->stream));
+    HIP_CHECK(hipMemcpyAsync(x->d_flv_states.ptr, states, (size_t)n_streams * sizeof(edgpu_flv_state), hipMemcpyHostToDevice, x->stream));
+    if (!device_es && es_bytes) HIP_CHECK(hipMemcpyAsync(x->d_flv_es.ptr, es, es_bytes, hipMemcpyHostToDevice, x->stream));
+    if (covered != n_units) HIP_CHECK(hipMemsetAsync(x->d_flv_recs.ptr, 0, (size_t)n_units * sizeof(FlvRec), x->stream));
+    HIP_CHECK(wsync(x, x->stream));             // `ranges` is on the stack
+    FlvParams p;
+    p.sc.es = device_es ? (const uint8_t*)es : x->d_flv_es.ptr;
+    p.sc.es_bytes = es_bytes;
+    p.sc.bitmap = x->d_flv_bitmap.ptr; p.sc.chunk_first = x->d_flv_chunks.ptr; p.sc.lens = x->d_flv_lens.ptr;
+    p.sc.nwords = nwords; p.sc.nchunks = nchunks;
+    p.units = x->d_flv_units_in.ptr; p.ranges = x->d_flv_ranges.ptr;
+    p.states = x->d_flv_states.ptr; p.new_states = x->d_flv_states.ptr + n_streams;
+    p.recs = x->d_flv_recs.ptr; p.srecs = x->d_flv_srecs.ptr;
+    p.place = x->d_flv_place;
+    p.out = device_out ? (uint8_t*)out : x->d_flv_out.ptr;
+    p.rows = x->d_flv_rows.ptr;
+    p.out_cap = out_cap;
+    p.time_offset = c.time_offset;
+    p.n_units = n_units; p.n_streams = n_streams;
+    HIP_CHECK(hist_mark(x, 8, 0));
+    HIP_CHECK(launch_flv_mux(p, (uint32_t)std::max(x->num_cus * 8, 1), x->stream));
+    HIP_CHECK(hist_mark(x, 8, 1));
+    FlvPlace pl;
+    {
+        Readback rb(x);
+        HIP_CHECK(rb.add(&pl, x->d_flv_place, sizeof(pl)));
+        HIP_CHECK(rb.run());
+    }
+    result->bytes = pl.bytes;
+    if (!pl.commit)
+        return fail(EDGPU_OUT_OVERFLOW, "FLV mux: " + std::to_string(pl.bytes) + " bytes needed; nothing was written");
+    std::vector<FlvStreamRec> runs;
+    if (!device_out) {                          // the bytes between two runs are not the caller's to lose
+        runs.resize(n_streams);
+        Readback rr(x);
+        HIP_CHECK(rr.add(runs.data(), x->d_flv_srecs.ptr, (size_t)n_streams * sizeof(FlvStreamRec)));
+        HIP_CHECK(rr.run());
+    }
+    Readback rb(x);
+    for (size_t s = 0; s < runs.size();) {
+        uint64_t a = runs[s].base, b = a + runs[s].bytes;
+        for (s++; s < runs.size() && runs[s].base == b; s++) b += runs[s].bytes;   // runs that touch: one copy
+        if (b > a) HIP_CHECK(rb.add((uint8_t*)out + a, x->d_flv_out.ptr + a, b - a));
+    }
+    HIP_CHECK(rb.add(tags, x->d_flv_rows.ptr, (size_t)n_units * sizeof(edgpu_flv_tag)));
+    HIP_CHECK(rb.add(states, x->d_flv_states.ptr + n_streams, (size_t)n_streams * sizeof(edgpu_flv_state)));
+    HIP_CHECK(rb.run());
+    return EDGPU_OK;
+}
+
 int edgpu_kernel_times(edgpu_ctx* x, int which, float* out_ms, uint32_t max_n, uint32_t* out_n) {
-    if (!x || which < 0 || which > 7 || (!out_ms && max_n)) return fail(EDGPU_BAD_ARGUMENT, "bad argument");
+    if (!x || which < 0 || which > 8 || (!out_ms && max_n)) return fail(EDGPU_BAD_ARGUMENT, "bad argument");
     DEVICE_ENTER(x);
     HIP_CHECK(sync_all(x));
     const uint32_t n = std::min<uint32_t>(x->hist_n[which] - x->hist_rd[which], edgpu_ctx::kHist);

@@ -2,18 +2,9 @@
 // stated in include/edgpu.h (edgpu_mp4_mux) and restated on the CPU in tests/mp4_model.py.  One call
 // is six kernels:
 //
-//   k_mp4_mark     flat over the ES, a lane per 32 bytes (two aligned 16-B loads and the dword after
-//                  them): one word of the start-code bitmap -- bit b of word w says 00 00 00 01 begins
-//                  at ES byte 32 w + b.  A wave is a chunk of 2 KiB; it also leaves the chunk's first
-//                  start code.  The bitmap knows nothing of units: a start code that straddles a
-//                  unit's end is told apart where it is used.
-//   k_mp4_resolve  flat over the bitmap, a wave per chunk: for every start code the distance from
-//                  its end to the next one, into a table indexed by position / 4 (start codes are at
-//                  least 4 bytes apart).  The next one is in the lane's own word, in a later word of
-//                  the wave (one ballot), or -- for the chunk's last start code only -- in a later
-//                  chunk: the wave reads the chunks' first start codes 64 at a time, 128 KiB of ES
-//                  per step, so the search for a NAL of L bytes is L / 128 Ki + 1 steps and the
-//                  searches of a whole ES together read each chunk entry about once.
+//   k_mp4_mark     the bitmap of the ES's start codes and each 2-KiB chunk's first one
+//   k_mp4_resolve  for every start code the distance from its end to the next one (both are
+//                  edgpu_scode.h, shared with the FLV mux)
 //   k_mp4_plan     one wave64 per stream row, its units in rounds of 64: the extended timestamp, the
 //                  sample ranks, the fragment starts (first sample, key units, max_samples), each
 //                  sample's place in its fragment, the durations (the lane of a sample writes the
@@ -37,96 +28,17 @@
 #include "edgpu_params.h"
 #include "edgpu_bytes.h"
 #include "edgpu_wave.h"
+#include "edgpu_scode.h"
 
 namespace edgpu {
 namespace {
 
 constexpr uint32_t kMp4PlaceThreads = 256;
-constexpr uint32_t kChunkBytes = kMp4ChunkWords * 32;
-
-// Bits [lo, lo + 32) of the bitmap
-__device__ __forceinline__ uint32_t m_bits(const Mp4Params& P, uint64_t lo) {
-    const uint64_t w = lo >> 5;
-    const uint32_t sh = (uint32_t)(lo & 31u);
-    const uint32_t a = w < P.nwords ? P.bitmap[w] : 0u;
-    const uint32_t b = (sh && w + 1 < P.nwords) ? P.bitmap[w + 1] : 0u;
-    return (uint32_t)(((((uint64_t)b) << 32) | a) >> sh);
-}
-
 }  // namespace
 
-__global__ __launch_bounds__(256) void k_mp4_mark(Mp4Params P) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (uint64_t)gridDim.x * 4;
-    for (uint64_t c = wave; c < P.nchunks; c += nwaves) {
-        const uint64_t w = c * kMp4ChunkWords + lane;
-        const uint64_t pos = w << 5;
-        uint32_t bits = 0;
-        if (pos < P.es_bytes) {
-            const uint64_t left = P.es_bytes - pos;         // bytes at or past the ES end read as 0: they complete no start code
-            const u32x4* src = reinterpret_cast<const u32x4*>(P.es + pos);
-            u32x4 v0 = src[0];
-            u32x4 v1 = left > 16 ? src[1] : u32x4{0u, 0u, 0u, 0u};
-            uint32_t nx = left > 32 ? *reinterpret_cast<const uint32_t*>(P.es + pos + 32) : 0u;
-            if (left < 16) v0 = keep16(v0, (int)left);
-            else if (left < 32) v1 = keep16(v1, (int)left - 16);
-            else if (left < 36) nx &= (1u << (8 * ((uint32_t)left - 32))) - 1u;
-            const uint32_t d[9] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, nx};
-#pragma unroll
-            for (uint32_t j = 0; j < 8; j++) {
-                const uint32_t lo = d[j], hi = d[j + 1];
-                if (lo == 0x01000000u) bits |= 1u << (4 * j);
-                if (__builtin_amdgcn_alignbyte(hi, lo, 1) == 0x01000000u) bits |= 2u << (4 * j);
-                if (__builtin_amdgcn_alignbyte(hi, lo, 2) == 0x01000000u) bits |= 4u << (4 * j);
-                if (__builtin_amdgcn_alignbyte(hi, lo, 3) == 0x01000000u) bits |= 8u << (4 * j);
-            }
-        }
-        if (w < P.nwords) P.bitmap[w] = bits;
-        const uint64_t ball = __ballot(bits != 0);
-        if (ball == 0) {
-            if (lane == 0) P.chunk_first[c] = kMp4None;
-        } else if (lane == (uint32_t)__builtin_ctzll(ball)) {
-            P.chunk_first[c] = lane * 32u + (uint32_t)__builtin_ctz(bits);
-        }
-    }
-}
+__global__ __launch_bounds__(256) void k_mp4_mark(Mp4Params P) { scode_mark(P.sc); }
 
-__global__ __launch_bounds__(256) void k_mp4_resolve(Mp4Params P) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (uint64_t)gridDim.x * 4;
-    for (uint64_t c = wave; c < P.nchunks; c += nwaves) {
-        const uint64_t w = c * kMp4ChunkWords + lane;
-        const uint32_t bits = w < P.nwords ? P.bitmap[w] : 0u;
-        const uint64_t ball = __ballot(bits != 0);
-        if (ball == 0) continue;                            // wave-uniform
-        // the next word of this wave that holds a start code
-        const uint64_t above = lane == 63 ? 0ull : ball & ~((2ull << lane) - 1ull);
-        const uint32_t nl = above ? (uint32_t)__builtin_ctzll(above) : 0u;
-        const uint32_t fb = bits ? (uint32_t)__builtin_ctz(bits) : 0u;
-        const uint32_t nfb = (uint32_t)__shfl((int)fb, (int)nl, 64);
-        // the chunk's last start code looks at the later chunks, 64 per step
-        uint64_t far = P.es_bytes;
-        for (uint64_t cc = c + 1; cc < P.nchunks; cc += 64) {
-            const uint32_t v = cc + lane < P.nchunks ? P.chunk_first[cc + lane] : kMp4None;
-            const uint64_t b2 = __ballot(v != kMp4None);
-            if (b2) {
-                const uint32_t l2 = (uint32_t)__builtin_ctzll(b2);
-                far = (cc + l2) * kChunkBytes + lane_of(v, l2);
-                break;
-            }
-        }
-        const uint64_t after = above ? (c * kMp4ChunkWords + nl) * 32ull + nfb : far;
-        uint32_t rem = bits;
-        while (rem) {
-            const uint32_t i = (uint32_t)__builtin_ctz(rem);
-            rem &= rem - 1;
-            const uint64_t q = (w << 5) + i;
-            const uint64_t nxt = rem ? (w << 5) + (uint32_t)__builtin_ctz(rem) : after;
-            const uint64_t dist = nxt - (q + 4);
-            P.lens[q >> 2] = dist > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)dist;
-        }
-    }
-}
+__global__ __launch_bounds__(256) void k_mp4_resolve(Mp4Params P) { scode_resolve(P.sc); }
 
 __global__ __launch_bounds__(64) void k_mp4_plan(Mp4Params P) {
     const uint32_t s = blockIdx.x;
@@ -153,7 +65,7 @@ __global__ __launch_bounds__(64) void k_mp4_plan(Mp4Params P) {
         }
         const bool hasb = bytes != 0;
         const uint32_t has = hasb ? 1u : 0u;
-        if (hasb && !(bytes >= 4 && ((P.bitmap[off >> 5] >> (off & 31u)) & 1u))) flags |= EDGPU_TAP_DAMAGED;
+        if (hasb && !(bytes >= 4 && ((P.sc.bitmap[off >> 5] >> (off & 31u)) & 1u))) flags |= EDGPU_TAP_DAMAGED;
         // the extended timestamp, as the transport-stream mux extends it
         uint32_t prev_ts = __shfl_up(ts, 1, 64);
         if (lane == 0) prev_ts = (uint32_t)c_ext;
@@ -452,24 +364,6 @@ __device__ __forceinline__ uint32_t m_hdr_word(const Mp4Params& P, const Mp4Cur&
     }
 }
 
-// Byte `t` of the current sample: a byte of a NAL length where a start code was, else the ES byte
-__device__ __forceinline__ uint32_t m_sample_byte(const Mp4Params& P, const Mp4Cur& c, uint32_t t) {
-    const uint64_t a = c.s_src, end = c.s_src + c.s_bytes, sp = a + t;
-    const uint64_t lo = sp >= 3 ? sp - 3 : 0;
-    const uint32_t v = m_bits(P, lo);
-#pragma unroll
-    for (uint32_t j = 0; j < 4; j++) {
-        if (sp < lo + j) continue;
-        const uint64_t q = sp - j;
-        if (q < a || q + 4 > end || !((v >> (uint32_t)(q - lo)) & 1u)) continue;
-        const uint64_t q2 = q + 4 + P.lens[q >> 2];
-        const uint64_t nal_end = q2 + 4 <= end ? q2 : end;  // a start code cut by the unit's end is data
-        const uint32_t len = (uint32_t)(nal_end - (q + 4));
-        return (len >> (8 * (3 - j))) & 0xFFu;
-    }
-    return P.es[sp];
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(256) void k_mp4_pack(Mp4Params P) {
@@ -501,10 +395,8 @@ __global__ __launch_bounds__(256) void k_mp4_pack(Mp4Params P) {
             const uint64_t t = rel - c.s_off;
             if (t + 16 <= c.s_bytes) {
                 const uint64_t sp = c.s_src + t;
-                const uint64_t b0 = sp >= 3 ? sp - 3 : 0;   // a start code that begins in [sp - 3, sp + 15] touches the word
-                const uint32_t nb = (uint32_t)(sp + 16 - b0);
-                if ((m_bits(P, b0) & ((1u << nb) - 1u)) == 0) {
-                    const uintptr_t a = (uintptr_t)(P.es + sp);
+                if (scode_clear16(P.sc, sp)) {
+                    const uintptr_t a = (uintptr_t)(P.sc.es + sp);
                     const uint32_t sh = (uint32_t)(a & 15u);
                     const u32x4* sw = reinterpret_cast<const u32x4*>(a & ~(uintptr_t)15);
                     const u32x4 l = sw[0];
@@ -532,7 +424,7 @@ __global__ __launch_bounds__(256) void k_mp4_pack(Mp4Params P) {
                 const uint64_t r2 = c.foff + x;
                 if (c.k == kMp4None) m_find_sample(P, c, r2);
                 else if (r2 >= c.s_off + c.s_bytes) m_load_sample(P, c, c.k + 1);
-                v = m_sample_byte(P, c, (uint32_t)(r2 - c.s_off));
+                v = scode_sample_byte(P.sc, c.s_src, c.s_bytes, (uint32_t)(r2 - c.s_off));
             }
             v <<= 8 * (i & 3u);
             const uint32_t dw = i >> 2;
@@ -554,8 +446,8 @@ __global__ __launch_bounds__(256) void k_mp4_pack(Mp4Params P) {
 }
 
 hipError_t launch_mp4_mux(const Mp4Params& p, uint32_t flat_blocks, hipStream_t st) {
-    if (p.nchunks) {
-        const uint32_t mb = (uint32_t)((p.nchunks + 3) / 4 < flat_blocks ? (p.nchunks + 3) / 4 : flat_blocks);
+    if (p.sc.nchunks) {
+        const uint32_t mb = (uint32_t)((p.sc.nchunks + 3) / 4 < flat_blocks ? (p.sc.nchunks + 3) / 4 : flat_blocks);
         EDGPU_LAUNCH(k_mp4_mark, dim3(mb), dim3(256), 0, st, p);
         EDGPU_LAUNCH(k_mp4_resolve, dim3(mb), dim3(256), 0, st, p);
     }

@@ -262,12 +262,26 @@ struct TsParams {
 };
 hipError_t launch_ts_mux(const TsParams& p, uint32_t pack_blocks, hipStream_t st);
 
+// The start codes of an elementary stream, as the fragmented-MP4 and the FLV mux find them
+// (edgpu_scode.h): a bitmap of every 00 00 00 01 and the distance from each to the next.
+constexpr uint32_t kScodeNone = 0xFFFFFFFFu;
+constexpr uint32_t kScodeChunkWords = 64;   // bitmap words (of 32 ES bytes) one wave marks: a chunk is 2 KiB of ES
+constexpr uint32_t kScodeChunkBytes = kScodeChunkWords * 32;
+struct ScodeView {
+    const uint8_t* es;
+    uint64_t es_bytes;
+    uint32_t* bitmap;           // nwords: bit b of word w: a start code begins at ES byte 32 w + b
+    uint32_t* chunk_first;      // nchunks: the chunk's first start code, relative, or kScodeNone
+    uint32_t* lens;             // es_bytes / 4 + 1: at [q >> 2], the bytes from start code q's end to the next start code (or the ES end)
+    uint64_t nwords, nchunks;
+};
+
 // The fragmented-MP4 mux (edgpu_mp4_mux, edgpu_mp4.hip): k_mp4_mark and k_mp4_resolve (flat over the
 // ES: the start codes and the distance from each to the next), k_mp4_plan (a wave per stream row),
 // k_mp4_place (one workgroup), k_mp4_rows (flat over fragments and units) and k_mp4_pack (flat over
 // the output's 16-B words).
 constexpr uint32_t kMp4None = 0xFFFFFFFFu;
-constexpr uint32_t kMp4ChunkWords = 64;     // bitmap words (of 32 ES bytes) one wave marks: a chunk is 2 KiB of ES
+constexpr uint32_t kMp4ChunkWords = kScodeChunkWords;
 struct Mp4Range { uint32_t first, count, slot, _pad; };   // slot: the row's first Mp4FragRec (the rows before it hold count + 1 each)
 struct Mp4Rec {                 // per unit, from k_mp4_plan; zero for a unit no row covers
     uint64_t dts;
@@ -292,16 +306,11 @@ struct Mp4StreamRec { uint64_t bytes, base; uint32_t nfrags, fbase; };
 struct Mp4Samp { uint64_t off; uint32_t unit, _pad; };      // a stream's samples in order: offset in the stream's run
 struct Mp4Place { uint64_t bytes; uint32_t frags, commit; };
 struct Mp4Params {
-    const uint8_t* es;
-    uint64_t es_bytes;
+    ScodeView sc;               // the ES and its start codes
     const edgpu_tap_unit* units;
     const Mp4Range* ranges;
     const edgpu_mp4_state* states;
     edgpu_mp4_state* new_states;
-    uint32_t* bitmap;           // nwords: bit b of word w: a start code begins at ES byte 32 w + b
-    uint32_t* chunk_first;      // nchunks: the chunk's first start code, relative, or kMp4None
-    uint32_t* lens;             // es_bytes / 4 + 1: at [q >> 2], the bytes from start code q's end to the next start code (or the ES end)
-    uint64_t nwords, nchunks;
     Mp4Rec* recs;               // n_units
     Mp4FragRec* frecs;          // n_units + n_streams
     Mp4StreamRec* srecs;        // n_streams
@@ -316,6 +325,37 @@ struct Mp4Params {
     uint32_t max_samples, default_duration;
 };
 hipError_t launch_mp4_mux(const Mp4Params& p, uint32_t flat_blocks, hipStream_t st);
+
+// The FLV mux (edgpu_flv_mux, edgpu_flv.hip): k_flv_mark and k_flv_resolve (the start codes, as the
+// fragmented-MP4 mux finds them), k_flv_plan (a wave per stream row), k_flv_place (one workgroup)
+// and k_flv_pack (flat over the output's 16-B words, then over the tag rows).
+struct FlvRange { uint32_t first, count; };
+struct FlvRec {                 // per unit, from k_flv_plan; zero for a unit no row covers
+    uint32_t pre;               // of its tag, relative to the stream's run
+    uint32_t ts_ms;
+    uint32_t flags;             // the tag row's | kind << 30: 0 uncovered, 1 no bytes, 2 a tag
+    uint32_t stream;
+    uint32_t sps_offset, sps_bytes, pps_offset, pps_bytes;
+};
+static_assert(sizeof(FlvRec) == 32, "FlvRec layout");
+struct FlvStreamRec { uint64_t bytes, base; };
+struct FlvPlace { uint64_t bytes; uint32_t commit, _pad; };
+struct FlvParams {
+    ScodeView sc;               // the ES and its start codes
+    const edgpu_tap_unit* units;
+    const FlvRange* ranges;
+    const edgpu_flv_state* states;
+    edgpu_flv_state* new_states;
+    FlvRec* recs;               // n_units
+    FlvStreamRec* srecs;        // n_streams
+    FlvPlace* place;
+    uint8_t* out;
+    edgpu_flv_tag* rows;        // n_units
+    uint64_t out_cap;
+    uint64_t time_offset;
+    uint32_t n_units, n_streams;
+};
+hipError_t launch_flv_mux(const FlvParams& p, uint32_t flat_blocks, hipStream_t st);
 
 struct ImageParams {
     SenderDev* senders;

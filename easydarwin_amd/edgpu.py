@@ -47,6 +47,7 @@ EXPORTED = [
     "edgpu_stream_stats_enable", "edgpu_stream_stats_disable", "edgpu_stream_stats_sample",
     "edgpu_stream_stats_get", "edgpu_session_bitrate",
     "edgpu_tap_enable", "edgpu_tap_disable", "edgpu_tap_drain", "edgpu_ts_mux",
+    "edgpu_flv_mux", "edgpu_flv_header",
 ]
 # the fragmented-MP4 entry points, listed apart: tests/test_abi.py compares EXPORTED with the names its
 # pattern finds in the header, and that pattern stops at a digit (tests/test_mp4_abi.py checks these)
@@ -251,6 +252,30 @@ class Mp4Result(C.Structure):
 
 MP4_NO_FRAGMENT = 0xFFFFFFFF
 
+
+class FlvConfig(C.Structure):
+    """edgpu_flv_config"""
+    _fields_ = [("time_offset", C.c_uint64), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class FlvState(C.Structure):
+    """edgpu_flv_state: what the FLV mux carries per stream between calls; the caller holds it."""
+    _fields_ = [("ext_ts", C.c_uint64), ("origin", C.c_uint64), ("started", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class FlvTag(C.Structure):
+    """edgpu_flv_tag: where one input unit's tag is, and the parameter sets in it."""
+    _fields_ = [("offset", C.c_uint64), ("bytes", C.c_uint32), ("timestamp_ms", C.c_uint32), ("flags", C.c_uint32),
+                ("stream", C.c_uint32), ("sps_offset", C.c_uint32), ("sps_bytes", C.c_uint32), ("pps_offset", C.c_uint32),
+                ("pps_bytes", C.c_uint32)]
+
+
+class FlvResult(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("units", C.c_uint32), ("streams", C.c_uint32)]
+
+
+FLV_FILE, FLV_META, FLV_SEQ = 1, 2, 4
+
 TS_AUD, TS_NOAUD = 1, 2
 TS_PACKET = 188
 
@@ -273,6 +298,10 @@ MP4_SAMPLE_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in Mp4Sample._fields_
 MP4_FRAG_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in Mp4Frag._fields_])
 assert MP4_STATE_DTYPE.itemsize == C.sizeof(Mp4State) == 32 and MP4_SAMPLE_DTYPE.itemsize == C.sizeof(Mp4Sample) == 32
 assert MP4_FRAG_DTYPE.itemsize == C.sizeof(Mp4Frag) == 48 and C.sizeof(Mp4Config) == 24 and C.sizeof(Mp4Result) == 24
+FLV_STATE_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in FlvState._fields_])
+FLV_TAG_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in FlvTag._fields_])
+assert FLV_STATE_DTYPE.itemsize == C.sizeof(FlvState) == 24 and FLV_TAG_DTYPE.itemsize == C.sizeof(FlvTag) == 40
+assert C.sizeof(FlvConfig) == 16 and C.sizeof(FlvResult) == 16
 PKT_DTYPE = np.dtype([("slot", "<u4"), ("len", "<u2"), ("channel", "u1"), ("flags", "u1"),
                       ("arrival_ms", "<i8")])
 OUT_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u4"), ("packet_id", "<u4")])
@@ -400,6 +429,8 @@ def load(path: str = LIB_PATH):
         "edgpu_mp4_mux": (I32, [P, C.POINTER(Mp4Config), P, U64, I32, P, U32, P, U32, P, P, U64, I32, P, P, U32,
                                 C.POINTER(Mp4Result)]),
         "edgpu_mp4_init": (I32, [P, U32, P, U32, U32, P, U64, C.POINTER(U64)]),
+        "edgpu_flv_mux": (I32, [P, C.POINTER(FlvConfig), P, U64, I32, P, U32, P, U32, P, P, U64, I32, P, C.POINTER(FlvResult)]),
+        "edgpu_flv_header": (I32, [P, U32, P, U32, U32, U32, P, U64, C.POINTER(U64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -450,6 +481,21 @@ def mp4_init(sps: bytes, pps: bytes, timescale: int = 0) -> bytes:
     if rc != 0:
         raise EdgpuError(rc, "edgpu_mp4_init: " + ("the buffer is too small" if rc == OUT_OVERFLOW else
                                                   "not an SPS and a PPS, or the SPS does not parse"))
+    return buf.raw[:n.value]
+
+
+def flv_header(sps: bytes, pps: bytes, timestamp_ms: int = 0, parts: int = 0) -> bytes:
+    """What stands before the tags of an FLV stream (edgpu_flv_header): the file header, onMetaData and
+    the AVC sequence header at `timestamp_ms`, or those of them `parts` names (FLV_FILE | FLV_META |
+    FLV_SEQ; 0: all).  `sps` and `pps` are one NAL each, without start code.  Host only."""
+    lib = load()
+    sps, pps = bytes(sps), bytes(pps)
+    n = C.c_uint64()
+    buf = C.create_string_buffer(256 + len(sps) + len(pps))
+    rc = lib.edgpu_flv_header(sps, len(sps), pps, len(pps), timestamp_ms & 0xFFFFFFFF, parts, buf, len(buf), C.byref(n))
+    if rc != 0:
+        raise EdgpuError(rc, "edgpu_flv_header: " + ("the buffer is too small" if rc == OUT_OVERFLOW else
+                                                    "not an SPS and a PPS, the SPS does not parse, or unknown parts"))
     return buf.raw[:n.value]
 
 
@@ -506,6 +552,8 @@ class Context:
             del self._ts_states[k]
         for k in [k for k in getattr(self, "_mp4_states", {}) if k[0] == session]:
             del self._mp4_states[k]
+        for k in [k for k in getattr(self, "_flv_states", {}) if k[0] == session]:
+            del self._flv_states[k]
 
     def subscriber_add(self, session: int, transport: int = TRANSPORT_UDP) -> int:
         out = C.c_uint32()
@@ -700,6 +748,7 @@ class Context:
         _check(self.lib.edgpu_tap_disable(self.h, session, track))
         getattr(self, "_ts_states", {}).pop((session, track), None)
         getattr(self, "_mp4_states", {}).pop((session, track), None)
+        getattr(self, "_flv_states", {}).pop((session, track), None)
 
     def tap_drain_raw(self, flags, out_ptr, out_cap, ptr_kind, units: np.ndarray, streams: np.ndarray) -> tuple:
         """edgpu_tap_drain as it is: (status, TapResult)."""
@@ -849,6 +898,64 @@ class Context:
             self._mp4_states[k] = states[i].copy()
         return out[:mres.bytes], samples, frags[:mres.frags], units, streams
 
+    def flv_mux_raw(self, cfg, es_ptr, es_bytes, es_kind, units: np.ndarray, streams: np.ndarray, states: np.ndarray,
+                    out_ptr, out_cap, out_kind, tags: np.ndarray) -> tuple:
+        """edgpu_flv_mux as it is: (status, FlvResult).  `units` / `streams` are TAP_UNIT_DTYPE /
+        TAP_STREAM_DTYPE rows, `states` FLV_STATE_DTYPE rows (in / out), `tags` FLV_TAG_DTYPE rows (one
+        per unit)."""
+        res = FlvResult()
+        rc = self.lib.edgpu_flv_mux(self.h, C.byref(cfg) if cfg is not None else None, C.c_void_p(es_ptr), es_bytes, es_kind,
+                                    _ptr(units) if len(units) else None, len(units),
+                                    _ptr(streams) if len(streams) else None, len(streams),
+                                    _ptr(states) if len(states) else None,
+                                    C.c_void_p(out_ptr), out_cap, out_kind,
+                                    _ptr(tags) if len(tags) else None, C.byref(res))
+        return rc, res
+
+    def tap_drain_flv(self, flush: bool = False, cfg=None):
+        """Drains every enabled tap into device memory and muxes the units into FLV video tags there
+        (edgpu_tap_drain, edgpu_flv_mux): (bytes, tags, units, streams) -- a uint8 array holding each
+        stream's run of tags, FLV_TAG_DTYPE rows (one per drained unit), and the drain's unit and
+        stream rows.  The mux's state rows are kept here by (session, track); tap_disable and
+        session_remove drop them."""
+        if not hasattr(self, "_flv_states"):
+            self._flv_states = {}
+        if getattr(self, "_flv_es", None) is None:
+            self._flv_es = self.device_alloc(1 << 20)
+        caps = getattr(self, "_tap_caps", [1 << 20, 4096, 64])
+        for attempt in range(2):
+            units = np.zeros(caps[1], dtype=TAP_UNIT_DTYPE)
+            streams = np.zeros(caps[2], dtype=TAP_STREAM_DTYPE)
+            rc, res = self.tap_drain_raw(TAP_FLUSH if flush else 0, self._flv_es.ptr, self._flv_es.nbytes, PTR_DEVICE, units, streams)
+            if rc != OUT_OVERFLOW or attempt:
+                break
+            caps = [caps[0], max(caps[1], int(res.units)), max(caps[2], int(res.streams))]
+            self._tap_caps = caps
+            if res.bytes > self._flv_es.nbytes:
+                self._flv_es.free()
+                self._flv_es = None
+                self._flv_es = self.device_alloc(max(int(res.bytes), 2 * caps[0]))
+        _check(rc)
+        units, streams = units[:res.units], streams[:res.streams]
+        keys = [(int(st["session"]), int(st["track"])) for st in streams]
+        states = np.zeros(len(streams), dtype=FLV_STATE_DTYPE)
+        for i, k in enumerate(keys):
+            if k in self._flv_states:
+                states[i] = self._flv_states[k]
+        tags = np.zeros(len(units), dtype=FLV_TAG_DTYPE)
+        cap = getattr(self, "_flv_cap", 1 << 20)
+        for attempt in range(2):
+            out = np.empty(cap, dtype=np.uint8)
+            rc, fres = self.flv_mux_raw(cfg, self._flv_es.ptr, int(res.bytes), PTR_DEVICE, units, streams, states,
+                                        out.ctypes.data, out.nbytes, PTR_HOST, tags)
+            if rc != OUT_OVERFLOW or attempt:
+                break
+            cap = self._flv_cap = max(int(fres.bytes), 2 * cap)
+        _check(rc)
+        for i, k in enumerate(keys):
+            self._flv_states[k] = states[i].copy()
+        return out[:fres.bytes], tags, units, streams
+
     def debug_stall(self, us: int):
         """edgpu_debug_stall: one wave on the context stream waits `us` microseconds of the device
         clock -- work the GPU watchdog (watchdog_ms) can time out on."""
@@ -877,7 +984,7 @@ class Context:
 
     def kernel_times(self, which: int) -> list:
         """which: 0 fan-out kernel, 1 whole fan-out tick, 2 ingest, 3 keyframe index, 4 stream statistics,
-        5 a tap drain, 6 a transport-stream mux, 7 a fragmented-MP4 mux."""
+        5 a tap drain, 6 a transport-stream mux, 7 a fragmented-MP4 mux, 8 an FLV mux."""
         buf = (C.c_float * 256)()
         n = C.c_uint32()
         _check(self.lib.edgpu_kernel_times(self.h, which, buf, 256, C.byref(n)))

@@ -876,7 +876,7 @@ int  edgpu_session_bitrate(edgpu_ctx* ctx, uint32_t session, uint32_t* bps);
  * pending-damage bit and the counters.  Taps belong to the owning context: they do not travel in
  * session images, a replica session starts without them, edgpu_session_remove clears them.
  * Out of scope: audio, packetization-mode 2, H.265, reordering.  (The drained units as an MPEG-2
- * transport stream: edgpu_ts_mux below; as fragmented MP4: edgpu_mp4_mux.) */
+ * transport stream: edgpu_ts_mux below; as fragmented MP4: edgpu_mp4_mux; as FLV tags: edgpu_flv_mux.) */
 #define EDGPU_TAP_KEY       1u
 #define EDGPU_TAP_PARAMS    2u
 #define EDGPU_TAP_DAMAGED   4u
@@ -972,7 +972,8 @@ int  edgpu_tap_drain(edgpu_ctx* ctx, uint32_t flags, void* out, uint64_t out_cap
  * Configuration: a field that is 0 takes its default, so `flags` 0 means EDGPU_TS_AUD;
  * EDGPU_TS_NOAUD alone turns the delimiter off; pcr_lead 0 means 63000.  PIDs above 0x1FFF, equal
  * PIDs or unknown flag bits are EDGPU_BAD_ARGUMENT.
- * Out of scope: audio PIDs, DTS / B-frames, H.265, SCTE markers.  (Fragmented MP4: edgpu_mp4_mux.) */
+ * Out of scope: audio PIDs, DTS / B-frames, H.265, SCTE markers.  (Fragmented MP4: edgpu_mp4_mux;
+ * FLV: edgpu_flv_mux.) */
 #define EDGPU_TS_AUD      1u
 #define EDGPU_TS_NOAUD    2u
 #define EDGPU_TS_PACKET 188u
@@ -1065,7 +1066,7 @@ int  edgpu_ts_mux(edgpu_ctx* ctx, const edgpu_ts_config* cfg /* NULL: defaults *
  * units total 2^31 bytes or more, or whose run could reach 2^32 bytes (its units' bytes + 108 per
  * unit: a fragment of one sample has 108 bytes of boxes).
  * Out of scope: audio tracks, B-frames / composition offsets, H.265, a trailing moov, sidx / mfra,
- * encryption. */
+ * encryption.  (The transport stream: edgpu_ts_mux; FLV: edgpu_flv_mux.) */
 typedef struct edgpu_mp4_config {    /* 0 in a field: the default */
     uint64_t time_offset;            /* added to every dts, 90 kHz */
     uint32_t max_samples;            /* per fragment; 0: no limit */
@@ -1125,12 +1126,102 @@ int  edgpu_mp4_mux(edgpu_ctx* ctx, const edgpu_mp4_config* cfg /* NULL: defaults
 int  edgpu_mp4_init(const uint8_t* sps, uint32_t sps_len, const uint8_t* pps, uint32_t pps_len, uint32_t timescale,
                     uint8_t* out, uint64_t cap, uint64_t* out_len);
 
+/* ---- FLV mux of tapped access units ----
+ *
+ * edgpu_flv_mux turns what edgpu_tap_drain returned into FLV video tags on the GPU, one per access
+ * unit and each complete by itself: after the bytes of edgpu_flv_header they are an .flv file or an
+ * HTTP-FLV response, and a tag's bytes from its 12th on (less the last four) are the body of an RTMP
+ * video message (easydarwin_amd/flv.py).  Latency is one access unit, not one segment.  As with
+ * edgpu_mp4_mux the caller holds one edgpu_flv_state row per stream (zero to start); the context
+ * keeps no table, and nothing is launched or allocated until the first call.  tests/flv_model.py is
+ * the executable statement of the rules below.
+ *
+ *   Order.  That of edgpu_mp4_mux: the streams in row order, each stream's run at the next 16-B
+ *     aligned offset of `out` (the bytes between two runs are not written); a stream's tags follow
+ *     each other without a gap, so a run is appended to a file or a response as it is.
+ *     result->bytes is the end of the last row's run.  The stream rows' unit ranges must ascend
+ *     without overlap; a unit no row covers gets a zero tag row.
+ *   Time.  ext and origin are exactly those of edgpu_mp4_mux (signed 32-bit steps; started == 0:
+ *     ext = rtp_ts and origin = ext).  t90 = (ext - origin + time_offset) mod 2^64 and
+ *     timestamp_ms = (t90 / 90) mod 2^32, the division unsigned and rounding down.  A unit with
+ *     bytes == 0 emits no tag: its row has bytes 0, the offset where its tag would begin, its
+ *     timestamp, the tap unit's flags and its stream row; it still advances ext and sets started.
+ *   Tag.  A unit of S ES bytes is a tag of S + 20 bytes: 09; BE24 DataSize = S + 5; BE24 the
+ *     timestamp's low 24 bits, then its bits 31..24; 00 00 00 (stream id); 17 for an EDGPU_TAP_KEY
+ *     unit, else 27 (frame type, codec 7); 01 (AVC NALU); 00 00 00 (composition time); the S sample
+ *     bytes; BE32 PreviousTagSize = S + 16.
+ *   Sample bytes.  The rule of edgpu_mp4_mux: every occurrence of 00 00 00 01 wholly inside the unit
+ *     is a start code (so in 00 00 00 00 01 the first byte is data, and 00 00 01 alone is data); it
+ *     is replaced by the big-endian 32-bit count of bytes from its end to the next start code or
+ *     the unit's end.  Every other byte is copied.  A unit with ES bytes that does not begin with a
+ *     start code keeps the bytes before its first one unchanged and its row gets EDGPU_TAP_DAMAGED.
+ *     All NALs stay in the tag.
+ *   Parameter sets.  For a unit with EDGPU_TAP_PARAMS (and ES bytes), among its first 8 NALs counted
+ *     from its first start code: the first NAL whose header & 0x1F is 7 and the first where it is 8,
+ *     each by the offset of its header byte relative to the tag's first byte and by its length.  A
+ *     parameter set beyond the eighth NAL is not reported, a NAL of length 0 never; bytes 0: none.
+ * No flags are defined: a non-zero `flags` is EDGPU_BAD_ARGUMENT, as is a unit of more than 0xFFFFFA
+ * bytes (DataSize is 24 bits) or a stream row whose run could reach 2^32 bytes (its units' bytes +
+ * 20 per unit).
+ * Out of scope: audio tags, B-frames / a non-zero composition time, H.265 / enhanced FLV, the HTTP
+ * and RTMP servers themselves, module prefs, taps on replica sessions, a method of the C++ adapter. */
+typedef struct edgpu_flv_config {
+    uint64_t time_offset;            /* added to every timestamp before the division, 90 kHz */
+    uint32_t flags;                  /* none defined */
+    uint32_t _pad;
+} edgpu_flv_config;
+typedef struct edgpu_flv_state {     /* per stream, caller-held, zero to start */
+    uint64_t ext_ts;                 /* extended RTP timestamp of the last unit muxed */
+    uint64_t origin;                 /* ext of the first unit ever */
+    uint32_t started, _pad;
+} edgpu_flv_state;
+typedef struct edgpu_flv_tag {       /* one per input unit, same index */
+    uint64_t offset;                 /* of the tag's first byte in `out` */
+    uint32_t bytes;                  /* unit bytes + 20; 0: no tag */
+    uint32_t timestamp_ms;
+    uint32_t flags;                  /* the tap unit's, | EDGPU_TAP_DAMAGED without a leading start code */
+    uint32_t stream;
+    uint32_t sps_offset, sps_bytes;  /* relative to `offset`; bytes 0: none */
+    uint32_t pps_offset, pps_bytes;
+} edgpu_flv_tag;
+typedef struct edgpu_flv_result { uint64_t bytes; uint32_t units, streams; } edgpu_flv_result;
+/* Muxes on the context stream and syncs.  Pointer kinds, the host arrays and the index checks are
+ * those of edgpu_ts_mux; `tags` has n_units rows.  When out_cap is too small the call returns
+ * EDGPU_OUT_OVERFLOW, `result` holds the bytes needed, and no byte of `out`, no row and no state is
+ * written: a retry with room gives what a first call would have given.  No byte outside a stream's
+ * run is written. */
+int  edgpu_flv_mux(edgpu_ctx* ctx, const edgpu_flv_config* cfg /* NULL: defaults */,
+                   const void* es, uint64_t es_bytes, int es_kind,
+                   const edgpu_tap_unit* units, uint32_t n_units,
+                   const edgpu_tap_stream* streams, uint32_t n_streams,
+                   edgpu_flv_state* states /* n_streams, in/out */,
+                   void* out, uint64_t out_cap, int out_kind,
+                   edgpu_flv_tag* tags /* n_units */, edgpu_flv_result* result);
+/* What stands before the tags, in up to three parts (`parts` 0: all three, in this order).  Host
+ * only: no context, nothing is launched.
+ *   EDGPU_FLV_FILE  the 13 bytes 46 4C 56 01 01 00 00 00 09 00 00 00 00: signature, version 1, video
+ *     only, header size, PreviousTagSize0.
+ *   EDGPU_FLV_META  a script tag (type 12, timestamp 0, DataSize 77; 92 bytes with its
+ *     PreviousTagSize) whose data is AMF0: the string "onMetaData" and an ECMA array of three
+ *     numbers, width, height and videocodecid (7), closed by 00 00 09.
+ *   EDGPU_FLV_SEQ   a video tag at timestamp_ms whose data is 17 00 00 00 00 and the
+ *     AVCDecoderConfigurationRecord: the AVC sequence header a decoder needs before the first tag.
+ * `sps` and `pps`, the record (byte for byte the payload of edgpu_mp4_init's avcC box) and width and
+ * height are those of edgpu_mp4_init, and so are the argument errors, unknown bits of `parts` among
+ * them, and the overflow convention: *out_len receives the size; when `cap` is smaller the call
+ * returns EDGPU_OUT_OVERFLOW and writes nothing else. */
+#define EDGPU_FLV_FILE 1u
+#define EDGPU_FLV_META 2u
+#define EDGPU_FLV_SEQ  4u
+int  edgpu_flv_header(const uint8_t* sps, uint32_t sps_len, const uint8_t* pps, uint32_t pps_len, uint32_t timestamp_ms,
+                      uint32_t parts, uint8_t* out, uint64_t cap, uint64_t* out_len);
+
 /* Per-launch device durations (ms, HIP events on the ctx stream) recorded since the last
  * call, oldest first, for `which` = 0 fan-out copy kernel, 1 whole fan-out tick (plan +
  * copy), 2 ingest (with the keyframe index it carries), 3 keyframe index (no entries since the
  * index runs inside the ingest kernel), 4 the stream-statistics kernel, 5 a tap drain's kernels,
- * 6 a transport-stream mux's kernels, 7 a fragmented-MP4 mux's kernels (4 to 7 recorded only at
- * EDGPU_TIMING_ALL).  Up to 256 launches are kept; the history is
+ * 6 a transport-stream mux's kernels, 7 a fragmented-MP4 mux's kernels, 8 an FLV mux's kernels (4 to
+ * 8 recorded only at EDGPU_TIMING_ALL).  Up to 256 launches are kept; the history is
  * cleared after reading.  Syncs. */
 int  edgpu_kernel_times(edgpu_ctx* ctx, int which, float* out_ms, uint32_t max_n, uint32_t* out_n);
 

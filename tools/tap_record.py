@@ -13,6 +13,10 @@ segment and then the fragments, cut by the same rule.  A stream whose SPS does n
 synthetic push and the test traces carry random bytes in their parameter sets) gets the
 initialisation segment of a stand-in 640x480 Baseline SPS, so that its file still opens; the report
 counts them in "stand_in_init".
+
+--flv records FLV (Context.tap_drain_flv, easydarwin_amd/flv.py): one video tag per access unit,
+muxed on the GPU, in <session>_<track>_<n>.flv behind the file header, onMetaData and the AVC sequence
+header, cut by the same rule; the stand-in parameter sets serve its headers in the same way.
 """
 import argparse
 import json
@@ -83,6 +87,23 @@ class StandInInit:
             return edgpu.mp4_init(STAND_IN_SPS, STAND_IN_PPS)
 
 
+class StandInHeader:
+    """The `header` callable of flv.Recorder: edgpu.flv_header, with the stand-in parameter sets
+    where it refuses the stream's own."""
+
+    def __init__(self):
+        self.count = 0
+
+    def __call__(self, sps, pps, timestamp_ms=0, parts=0):
+        try:
+            return edgpu.flv_header(sps, pps, timestamp_ms, parts)
+        except edgpu.EdgpuError as e:
+            if e.code != edgpu.BAD_ARGUMENT:
+                raise
+            self.count += 1
+            return edgpu.flv_header(STAND_IN_SPS, STAND_IN_PPS, timestamp_ms, parts)
+
+
 def synthetic(nsessions, seconds):
     tracks = [TrackSpec("video", "H264/90000", 96, bitrate=1_000_000, gop=30, idr_bytes=20_000),
               TrackSpec("audio", "PCMA/8000", 8)]
@@ -111,13 +132,20 @@ def main():
     ap.add_argument("--segment", type=float, default=300.0, help="seconds per file")
     ap.add_argument("--out", required=True)
     ap.add_argument("--mp4", action="store_true", help="record fragmented MP4 instead of Annex-B")
+    ap.add_argument("--flv", action="store_true", help="record FLV instead of Annex-B")
     a = ap.parse_args()
+    if a.mp4 and a.flv:
+        ap.error("--mp4 and --flv exclude each other")
     os.makedirs(a.out, exist_ok=True)
     sdps, pushes = from_trace(a.trace) if a.trace else synthetic(a.sessions, a.seconds)
     if a.mp4:
         from easydarwin_amd import mp4
         init = StandInInit()
         rec = mp4.Recorder(a.out, a.segment, init)
+    elif a.flv:
+        from easydarwin_amd import flv
+        init = StandInHeader()
+        rec = flv.Recorder(a.out, a.segment, init)
     else:
         rec = Recorder(a.out, int(a.segment * 1000))
     units = 0
@@ -149,10 +177,14 @@ def main():
                 data, samples, frags, rows, streams = ctx.tap_drain_mp4(flush=tick + a.tick_ms > end)
                 units += len(rows)
                 rec.push(data, samples, frags, streams)
+            elif a.flv:
+                data, tags, rows, streams = ctx.tap_drain_flv(flush=tick + a.tick_ms > end)
+                units += len(rows)
+                rec.push(data, tags, streams)
             else:
                 rec.take(*ctx.tap_drain(flush=tick + a.tick_ms > end))
     rec.close()
-    if a.mp4:
+    if a.mp4 or a.flv:
         print(json.dumps({"files": sum(len(v["files"]) for v in rec.summary().values()), "units": units,
                           "streams": rec.summary(), "stand_in_init": init.count}))
     else:
