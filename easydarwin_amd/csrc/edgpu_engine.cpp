@@ -341,23 +341,29 @@ struct edgpu_ctx {
     DevVec<edgpu_tap_unit> d_tap_units;
     DevVec<edgpu_tap_stream> d_tap_streams;
     TapPlace* d_tap_place = nullptr;
-    // the transport-stream mux (edgpu_ts_mux): staging only, allocated by the first call; the state
-    // between calls is the caller's
-    DevVec<uint8_t> d_ts_es, d_ts_out;
-    DevVec<edgpu_tap_unit> d_ts_units_in;
+    // The muxes of tapped units (edgpu_ts_mux, edgpu_mp4_mux, edgpu_flv_mux): staging and work
+    // buffers only, allocated by the first call and sized from each call's es_bytes and n_units;
+    // the state between calls is the caller's.  What every format needs is one set for all of them.
+    // That is safe: every mux call works on the context stream alone, so a call's copies into the
+    // set follow the kernels of the call before it, and every return after a launch -- committed or
+    // overflowed, the transport stream's second attempt too -- comes after a host wait on that
+    // stream (the read of the placement verdict, then the last Readback::run), so no call returns
+    // with work in flight on the set and a later call may grow (and so free) any of it.
+    struct MuxStaging {
+        DevVec<uint8_t> es, out;            // a host ES on its way in, a host `out` on its way back
+        DevVec<edgpu_tap_unit> units;
+        DevVec<uint32_t> bitmap, chunks, lens;   // the start codes (ScodeView): fragmented MP4 and FLV
+        void release() { es.release(); out.release(); units.release(); bitmap.release(); chunks.release(); lens.release(); }
+    } mux;
+    // typed per format; `states` are 2 x n_streams: the caller's rows, the new rows
     DevVec<TsRange> d_ts_ranges;
-    DevVec<edgpu_ts_state> d_ts_states;     // 2 x n_streams: the caller's rows, the new rows
+    DevVec<edgpu_ts_state> d_ts_states;
     DevVec<TsRec> d_ts_recs;
     DevVec<uint32_t> d_ts_base;
     DevVec<edgpu_ts_unit> d_ts_rows;
     uint8_t* d_ts_fixed = nullptr;          // TsPlace, then the PAT and PMT packet templates
-    // the fragmented-MP4 mux (edgpu_mp4_mux): staging and work buffers only, allocated by the first
-    // call and sized from each call's es_bytes and n_units; the state rows are the caller's
-    DevVec<uint8_t> d_mp4_es, d_mp4_out;
-    DevVec<uint32_t> d_mp4_bitmap, d_mp4_chunks, d_mp4_lens;
-    DevVec<edgpu_tap_unit> d_mp4_units_in;
     DevVec<Mp4Range> d_mp4_ranges;
-    DevVec<edgpu_mp4_state> d_mp4_states;   // 2 x n_streams: the caller's rows, the new rows
+    DevVec<edgpu_mp4_state> d_mp4_states;
     DevVec<Mp4Rec> d_mp4_recs;
     DevVec<Mp4FragRec> d_mp4_frecs;
     DevVec<Mp4StreamRec> d_mp4_srecs;
@@ -365,12 +371,8 @@ struct edgpu_ctx {
     DevVec<edgpu_mp4_sample> d_mp4_rows;
     DevVec<edgpu_mp4_frag> d_mp4_frags;
     Mp4Place* d_mp4_place = nullptr;
-    // the FLV mux (edgpu_flv_mux): staging and work buffers only, allocated by the first call
-    DevVec<uint8_t> d_flv_es, d_flv_out;
-    DevVec<uint32_t> d_flv_bitmap, d_flv_chunks, d_flv_lens;
-    DevVec<edgpu_tap_unit> d_flv_units_in;
     DevVec<FlvRange> d_flv_ranges;
-    DevVec<edgpu_flv_state> d_flv_states;   // 2 x n_streams: the caller's rows, the new rows
+    DevVec<edgpu_flv_state> d_flv_states;
     DevVec<FlvRec> d_flv_recs;
     DevVec<FlvStreamRec> d_flv_srecs;
     DevVec<edgpu_flv_tag> d_flv_rows;
@@ -683,17 +685,12 @@ int edgpu_ctx_destroy(edgpu_ctx* x) {
     x->d_taps.release(); x->d_tap_list.release(); x->d_tap_items.release(); x->d_tap_out.release();
     x->d_tap_units.release(); x->d_tap_streams.release();
     if (x->d_tap_place) (void)hipFree(x->d_tap_place);
-    x->d_ts_es.release(); x->d_ts_out.release(); x->d_ts_units_in.release(); x->d_ts_ranges.release();
-    x->d_ts_states.release(); x->d_ts_recs.release(); x->d_ts_base.release(); x->d_ts_rows.release();
-    if (x->d_ts_fixed) (void)hipFree(x->d_ts_fixed);
-    x->d_mp4_es.release(); x->d_mp4_out.release(); x->d_mp4_bitmap.release(); x->d_mp4_chunks.release(); x->d_mp4_lens.release();
-    x->d_mp4_units_in.release(); x->d_mp4_ranges.release(); x->d_mp4_states.release(); x->d_mp4_recs.release();
-    x->d_mp4_frecs.release(); x->d_mp4_srecs.release(); x->d_mp4_samps.release(); x->d_mp4_rows.release(); x->d_mp4_frags.release();
-    if (x->d_mp4_place) (void)hipFree(x->d_mp4_place);
-    x->d_flv_es.release(); x->d_flv_out.release(); x->d_flv_bitmap.release(); x->d_flv_chunks.release(); x->d_flv_lens.release();
-    x->d_flv_units_in.release(); x->d_flv_ranges.release(); x->d_flv_states.release(); x->d_flv_recs.release();
-    x->d_flv_srecs.release(); x->d_flv_rows.release();
-    if (x->d_flv_place) (void)hipFree(x->d_flv_place);
+    x->mux.release();
+    x->d_ts_ranges.release(); x->d_ts_states.release(); x->d_ts_recs.release(); x->d_ts_base.release(); x->d_ts_rows.release();
+    x->d_mp4_ranges.release(); x->d_mp4_states.release(); x->d_mp4_recs.release(); x->d_mp4_frecs.release(); x->d_mp4_srecs.release();
+    x->d_mp4_samps.release(); x->d_mp4_rows.release(); x->d_mp4_frags.release();
+    x->d_flv_ranges.release(); x->d_flv_states.release(); x->d_flv_recs.release(); x->d_flv_srecs.release(); x->d_flv_rows.release();
+    for (void* p : {(void*)x->d_ts_fixed, (void*)x->d_mp4_place, (void*)x->d_flv_place}) if (p) (void)hipFree(p);
     x->d_carry.release(); x->d_tcp_groups.release(); x->d_tcp_reads.release(); x->d_tcp_chunk_group.release();
     x->d_tcp_ncand.release(); x->d_tcp_cands.release(); x->d_tcp_links.release(); x->d_tcp_chunkres.release();
     x->d_tcp_results.release(); x->d_tcp_offs.release(); x->d_tcp_stage.release(); x->d_blocked.release();
@@ -2621,18 +2618,153 @@ static void ts_psi_packet(uint8_t* pkt, uint32_t pid, const uint8_t* section, si
     for (int i = 0; i < 4; i++) pkt[5 + n + i] = (uint8_t)(crc >> (24 - 8 * i));
 }
 
-int edgpu_ts_mux(edgpu_ctx* x, const edgpu_ts_config* cfg, const void* es, uint64_t es_bytes, int es_kind,
-                 const edgpu_tap_unit* units, uint32_t n_units, const edgpu_tap_stream* streams, uint32_t n_streams,
-                 edgpu_ts_state* states, void* out, uint64_t out_cap, int out_kind, edgpu_ts_unit* ts_units,
-                 edgpu_ts_result* result) {
-    if (!x || !result || (!es && es_bytes) || (!out && out_cap) || (!units && n_units) || (!ts_units && n_units) ||
+// ---- What the muxes of tapped units share (edgpu_ts_mux, edgpu_mp4_mux, edgpu_flv_mux) ----
+extern "C++" {                                  // (templates among them)
+// A mux call's arguments, as every format has them
+struct MuxCall {
+    const void* es; uint64_t es_bytes;
+    const edgpu_tap_unit* units; uint32_t n_units;
+    const edgpu_tap_stream* streams; uint32_t n_streams;
+    void* out; uint64_t out_cap;
+    bool device_es, device_out;
+};
+
+// Nulls against counts, pointer kinds, device alignment; `rows` and `states` are the format's
+static int mux_args(MuxCall* m, const edgpu_ctx* x, const void* result, const void* es, uint64_t es_bytes, int es_kind,
+                    const edgpu_tap_unit* units, uint32_t n_units, const edgpu_tap_stream* streams, uint32_t n_streams,
+                    const void* states, void* out, uint64_t out_cap, int out_kind, const void* rows) {
+    if (!x || !result || (!es && es_bytes) || (!out && out_cap) || (!units && n_units) || (!rows && n_units) ||
         (!streams && n_streams) || (!states && n_streams))
         return fail(EDGPU_BAD_ARGUMENT, "bad argument");
     for (int k : {es_kind, out_kind})
         if (k != EDGPU_PTR_HOST && k != EDGPU_PTR_DEVICE && k != EDGPU_PTR_PINNED) return fail(EDGPU_BAD_ARGUMENT, "bad pointer kind");
-    const bool device_es = es_kind == EDGPU_PTR_DEVICE, device_out = out_kind == EDGPU_PTR_DEVICE;
-    if ((device_es && ((uintptr_t)es & 15)) || (device_out && ((uintptr_t)out & 15)))
+    *m = MuxCall{es, es_bytes, units, n_units, streams, n_streams, out, out_cap, es_kind == EDGPU_PTR_DEVICE, out_kind == EDGPU_PTR_DEVICE};
+    if ((m->device_es && ((uintptr_t)es & 15)) || (m->device_out && ((uintptr_t)out & 15)))
         return fail(EDGPU_BAD_ARGUMENT, "device `es` and `out` must be 16-B aligned");
+    return EDGPU_OK;
+}
+
+// The rows the kernels index by, checked on the host: the units, then the streams' ranges.  Leaves
+// the format's range rows (`first` and `count`), the units the rows cover and, where asked, each
+// row's unit bytes; a format's own limits on them are its entry point's to check.
+template <typename Range>
+static int mux_check_rows(const MuxCall& m, std::vector<Range>* ranges, uint64_t* covered, std::vector<uint64_t>* totals) {
+    for (uint32_t i = 0; i < m.n_units; i++) {
+        if (m.units[i].stream >= m.n_streams) return fail(EDGPU_BAD_ARGUMENT, "a unit's stream index is out of range");
+        if (m.units[i].offset > m.es_bytes || m.units[i].bytes > m.es_bytes - m.units[i].offset)
+            return fail(EDGPU_BAD_ARGUMENT, "a unit reaches outside the ES bytes");
+    }
+    ranges->resize(m.n_streams);
+    if (totals) totals->assign(m.n_streams, 0);
+    uint64_t next = 0;
+    *covered = 0;
+    for (uint32_t s = 0; s < m.n_streams; s++) {
+        const uint64_t first = m.streams[s].unit_first, count = m.streams[s].unit_count;
+        if (first + count > m.n_units) return fail(EDGPU_BAD_ARGUMENT, "a stream's unit range reaches outside the units");
+        if (count) {
+            if (first < next) return fail(EDGPU_BAD_ARGUMENT, "the streams' unit ranges must ascend without overlap");
+            next = first + count;
+        }
+        if (totals)
+            for (uint64_t i = first; i < first + count; i++) (*totals)[s] += m.units[i].bytes;
+        (*ranges)[s] = Range{(uint32_t)first, (uint32_t)count};
+        *covered += count;
+    }
+    return EDGPU_OK;
+}
+
+// The result starts as the counts alone.  True without stream rows: every unit row is zero and the call is done.
+template <typename Result, typename Row>
+static bool mux_no_streams(const MuxCall& m, Result* result, Row* rows) {
+    memset(result, 0, sizeof(*result));
+    result->units = m.n_units; result->streams = m.n_streams;
+    if (!m.n_streams && m.n_units) memset(rows, 0, (size_t)m.n_units * sizeof(Row));
+    return !m.n_streams;
+}
+
+// Everything a launch reads, on the device: the shared staging and the format's ranges, states
+// (2 x n_streams: the caller's rows, the new rows) and unit records sized; units, ranges, states
+// and a host ES copied; the records zeroed when some unit is covered by no row; and one wait, which
+// keeps `ranges` (on the caller's stack) alive.  `out_staging`: bytes a host `out` is staged in.
+// `sc`: the ES and its start-code tables, for the formats that want them.
+template <typename Range, typename State, typename Rec>
+static int mux_upload(edgpu_ctx* x, const MuxCall& m, uint64_t out_staging, ScodeView* sc, const std::vector<Range>& ranges,
+                      DevVec<Range>& d_ranges, const State* states, DevVec<State>& d_states, DevVec<Rec>& d_recs, uint64_t covered) {
+    edgpu_ctx::MuxStaging& g = x->mux;
+    const size_t nu = std::max<uint32_t>(m.n_units, 1);
+    HIP_CHECK(g.units.reserve(nu, x->stream));
+    HIP_CHECK(d_recs.reserve(nu, x->stream));
+    HIP_CHECK(d_ranges.reserve(m.n_streams, x->stream));
+    HIP_CHECK(d_states.reserve(2 * (size_t)m.n_streams, x->stream));
+    if (sc) {
+        sc->es_bytes = m.es_bytes;
+        sc->nwords = (m.es_bytes + 31) / 32; sc->nchunks = (sc->nwords + kScodeChunkWords - 1) / kScodeChunkWords;
+        HIP_CHECK(g.bitmap.reserve(sc->nwords + 1, x->stream));
+        HIP_CHECK(g.chunks.reserve(sc->nchunks + 1, x->stream));
+        HIP_CHECK(g.lens.reserve(m.es_bytes / 4 + 1, x->stream));
+        sc->bitmap = g.bitmap.ptr; sc->chunk_first = g.chunks.ptr; sc->lens = g.lens.ptr;
+    }
+    if (!m.device_es) HIP_CHECK(g.es.reserve(m.es_bytes + 16, x->stream));
+    if (!m.device_out) HIP_CHECK(g.out.reserve(out_staging, x->stream));
+    if (sc) sc->es = m.device_es ? (const uint8_t*)m.es : g.es.ptr;
+    if (m.n_units) HIP_CHECK(hipMemcpyAsync(g.units.ptr, m.units, (size_t)m.n_units * sizeof(edgpu_tap_unit), hipMemcpyHostToDevice, x->stream));
+    HIP_CHECK(hipMemcpyAsync(d_ranges.ptr, ranges.data(), (size_t)m.n_streams * sizeof(Range), hipMemcpyHostToDevice, x->stream));
+    HIP_CHECK(hipMemcpyAsync(d_states.ptr, states, (size_t)m.n_streams * sizeof(State), hipMemcpyHostToDevice, x->stream));
+    if (!m.device_es && m.es_bytes) HIP_CHECK(hipMemcpyAsync(g.es.ptr, m.es, m.es_bytes, hipMemcpyHostToDevice, x->stream));
+    if (covered != m.n_units) HIP_CHECK(hipMemsetAsync(d_recs.ptr, 0, (size_t)m.n_units * sizeof(Rec), x->stream));
+    HIP_CHECK(wsync(x, x->stream));
+    return EDGPU_OK;
+}
+
+// One launch of a mux's kernels between the marks of timing ring `ring` (its events are created by
+// the first), and the placement verdict read back
+template <typename Params, typename Place>
+static int mux_launch(edgpu_ctx* x, int ring, hipError_t (*launch)(const Params&, uint32_t, hipStream_t), const Params& p, Place* pl) {
+    if (!x->hist[ring][0][0])
+        for (auto& s : x->hist[ring]) for (auto& e : s) HIP_CHECK(hipEventCreate(&e));
+    HIP_CHECK(hist_mark(x, ring, 0));
+    HIP_CHECK(launch(p, (uint32_t)std::max(x->num_cus * 8, 1), x->stream));
+    HIP_CHECK(hist_mark(x, ring, 1));
+    Readback rb(x);
+    HIP_CHECK(rb.add(pl, p.place, sizeof(*pl)));
+    HIP_CHECK(rb.run());
+    return EDGPU_OK;
+}
+
+// A host `out` of a format whose streams' runs are apart: the staged runs are read run by run, for
+// the bytes between two runs are not the caller's to lose.  `d_srecs`: the format's stream records,
+// `stride` bytes apart, each beginning with its run's bytes and base.
+static_assert(offsetof(Mp4StreamRec, bytes) == 0 && offsetof(Mp4StreamRec, base) == 8, "Mp4StreamRec begins with a run");
+static_assert(offsetof(FlvStreamRec, bytes) == 0 && offsetof(FlvStreamRec, base) == 8, "FlvStreamRec begins with a run");
+static int mux_read_runs(edgpu_ctx* x, const MuxCall& m, const void* d_srecs, size_t stride, Readback& rb) {
+    if (m.device_out) return EDGPU_OK;
+    std::vector<uint8_t> recs((size_t)m.n_streams * stride);
+    Readback rr(x);
+    HIP_CHECK(rr.add(recs.data(), d_srecs, recs.size()));
+    HIP_CHECK(rr.run());
+    struct Run { uint64_t bytes, base; } r;
+    for (uint32_t s = 0; s < m.n_streams;) {
+        memcpy(&r, &recs[s * stride], sizeof(r));
+        const uint64_t a = r.base;
+        uint64_t b = a + r.bytes;
+        for (s++; s < m.n_streams; s++) {                   // runs that touch: one copy
+            memcpy(&r, &recs[s * stride], sizeof(r));
+            if (r.base != b) break;
+            b += r.bytes;
+        }
+        if (b > a) HIP_CHECK(rb.add((uint8_t*)m.out + a, x->mux.out.ptr + a, b - a));
+    }
+    return EDGPU_OK;
+}
+}  // extern "C++"
+
+int edgpu_ts_mux(edgpu_ctx* x, const edgpu_ts_config* cfg, const void* es, uint64_t es_bytes, int es_kind,
+                 const edgpu_tap_unit* units, uint32_t n_units, const edgpu_tap_stream* streams, uint32_t n_streams,
+                 edgpu_ts_state* states, void* out, uint64_t out_cap, int out_kind, edgpu_ts_unit* ts_units,
+                 edgpu_ts_result* result) {
+    MuxCall m;
+    if (int rc = mux_args(&m, x, result, es, es_bytes, es_kind, units, n_units, streams, n_streams, states, out, out_cap, out_kind, ts_units))
+        return rc;
     edgpu_ts_config c;
     memset(&c, 0, sizeof(c));
     if (cfg) c = *cfg;
@@ -2644,33 +2776,11 @@ int edgpu_ts_mux(edgpu_ctx* x, const edgpu_ts_config* cfg, const void* es, uint6
     if (!c.pcr_lead) c.pcr_lead = 63000;
     if (c.pmt_pid > 0x1FFF || c.video_pid > 0x1FFF || c.pmt_pid == c.video_pid || (c.flags & ~(EDGPU_TS_AUD | EDGPU_TS_NOAUD)))
         return fail(EDGPU_BAD_ARGUMENT, "bad transport-stream configuration");
-    // the rows the kernels index by: checked here, on the host
-    std::vector<TsRange> ranges(n_streams);
-    uint64_t covered = 0, next = 0;
-    for (uint32_t s = 0; s < n_streams; s++) {
-        const uint64_t first = streams[s].unit_first, count = streams[s].unit_count;
-        if (first + count > n_units) return fail(EDGPU_BAD_ARGUMENT, "a stream's unit range reaches outside the units");
-        if (count) {
-            if (first < next) return fail(EDGPU_BAD_ARGUMENT, "the streams' unit ranges must ascend without overlap");
-            next = first + count;
-        }
-        ranges[s] = TsRange{(uint32_t)first, (uint32_t)count};
-        covered += count;
-    }
-    for (uint32_t i = 0; i < n_units; i++) {
-        if (units[i].stream >= n_streams) return fail(EDGPU_BAD_ARGUMENT, "a unit's stream index is out of range");
-        if (units[i].offset > es_bytes || units[i].bytes > es_bytes - units[i].offset)
-            return fail(EDGPU_BAD_ARGUMENT, "a unit reaches outside the ES bytes");
-    }
-    memset(result, 0, sizeof(*result));
-    result->units = n_units; result->streams = n_streams;
-    if (!n_streams) {
-        if (n_units) memset(ts_units, 0, (size_t)n_units * sizeof(edgpu_ts_unit));
-        return EDGPU_OK;
-    }
+    std::vector<TsRange> ranges;
+    uint64_t covered;
+    if (int rc = mux_check_rows(m, &ranges, &covered, nullptr)) return rc;
+    if (mux_no_streams(m, result, ts_units)) return EDGPU_OK;
     DEVICE_ENTER(x);
-    if (!x->hist[6][0][0])
-        for (auto& s : x->hist[6]) for (auto& e : s) HIP_CHECK(hipEventCreate(&e));
     constexpr size_t kTmplOff = 16;
     if (!x->d_ts_fixed && dmalloc(&x->d_ts_fixed, kTmplOff + 2 * EDGPU_TS_PACKET) != hipSuccess)
         return fail(EDGPU_OUT_OF_MEMORY, "transport-stream mux staging");
@@ -2684,58 +2794,41 @@ int edgpu_ts_mux(edgpu_ctx* x, const edgpu_ts_config* cfg, const void* es, uint6
         ts_psi_packet(tmpl, 0, pat, sizeof(pat));
         ts_psi_packet(tmpl + EDGPU_TS_PACKET, c.pmt_pid, pmt, sizeof(pmt));
     }
-    HIP_CHECK(x->d_ts_units_in.reserve(std::max<uint32_t>(n_units, 1), x->stream));
-    HIP_CHECK(x->d_ts_recs.reserve(std::max<uint32_t>(n_units, 1), x->stream));
     HIP_CHECK(x->d_ts_rows.reserve(std::max<uint32_t>(n_units, 1), x->stream));
-    HIP_CHECK(x->d_ts_ranges.reserve(n_streams, x->stream));
-    HIP_CHECK(x->d_ts_states.reserve(2 * (size_t)n_streams, x->stream));
     HIP_CHECK(x->d_ts_base.reserve((size_t)n_streams + 1, x->stream));
-    if (!device_es) HIP_CHECK(x->d_ts_es.reserve(es_bytes + 16, x->stream));
+    HIP_CHECK(hipMemcpyAsync(x->d_ts_fixed + kTmplOff, tmpl, sizeof(tmpl), hipMemcpyHostToDevice, x->stream));   // (on the stack until the upload's wait)
     // staging for the most the units can need (three packets of PSI and header overhead each), so
     // that a call with room plans once
-    if (!device_out)
-        HIP_CHECK(x->d_ts_out.reserve(std::min<uint64_t>(out_cap, (4ull * n_units + es_bytes / 184 + 1) * EDGPU_TS_PACKET), x->stream));
-    HIP_CHECK(hipMemcpyAsync(x->d_ts_fixed + kTmplOff, tmpl, sizeof(tmpl), hipMemcpyHostToDevice, x->stream));
-    if (n_units) HIP_CHECK(hipMemcpyAsync(x->d_ts_units_in.ptr, units, (size_t)n_units * sizeof(edgpu_tap_unit), hipMemcpyHostToDevice, x->stream));
-    HIP_CHECK(hipMemcpyAsync(x->d_ts_ranges.ptr, ranges.data(), (size_t)n_streams * sizeof(TsRange), hipMemcpyHostToDevice, x->stream));
-    HIP_CHECK(hipMemcpyAsync(x->d_ts_states.ptr, states, (size_t)n_streams * sizeof(edgpu_ts_state), hipMemcpyHostToDevice, x->stream));
-    if (!device_es && es_bytes) HIP_CHECK(hipMemcpyAsync(x->d_ts_es.ptr, es, es_bytes, hipMemcpyHostToDevice, x->stream));
-    if (covered != n_units) HIP_CHECK(hipMemsetAsync(x->d_ts_recs.ptr, 0, (size_t)n_units * sizeof(TsRec), x->stream));
-    HIP_CHECK(wsync(x, x->stream));             // `tmpl` and `ranges` are on the stack
+    const uint64_t most = (4ull * n_units + es_bytes / 184 + 1) * EDGPU_TS_PACKET;
+    if (int rc = mux_upload(x, m, std::min(out_cap, most), nullptr, ranges, x->d_ts_ranges, states, x->d_ts_states, x->d_ts_recs, covered))
+        return rc;
     TsPlace pl;
     for (int attempt = 0;; attempt++) {
         TsParams p;
-        p.es = device_es ? (const uint8_t*)es : x->d_ts_es.ptr;
-        p.units = x->d_ts_units_in.ptr; p.ranges = x->d_ts_ranges.ptr;
+        p.es = m.device_es ? (const uint8_t*)es : x->mux.es.ptr;
+        p.units = x->mux.units.ptr; p.ranges = x->d_ts_ranges.ptr;
         p.states = x->d_ts_states.ptr; p.new_states = x->d_ts_states.ptr + n_streams;
         p.recs = x->d_ts_recs.ptr; p.base = x->d_ts_base.ptr;
         p.place = reinterpret_cast<TsPlace*>(x->d_ts_fixed);
         p.tmpl = reinterpret_cast<const uint32_t*>(x->d_ts_fixed + kTmplOff);
-        p.out = device_out ? (uint8_t*)out : x->d_ts_out.ptr;
+        p.out = m.device_out ? (uint8_t*)out : x->mux.out.ptr;
         p.ts_units = x->d_ts_rows.ptr;
-        p.out_cap = device_out ? out_cap : std::min<uint64_t>(out_cap, x->d_ts_out.cap);
+        p.out_cap = m.device_out ? out_cap : std::min<uint64_t>(out_cap, x->mux.out.cap);
         p.pts_offset = c.pts_offset;
         p.n_units = n_units; p.n_streams = n_streams;
         p.pcr_lead = c.pcr_lead; p.video_pid = c.video_pid;
         p.aud = (c.flags & EDGPU_TS_AUD) ? 1u : 0u;
-        HIP_CHECK(hist_mark(x, 6, 0));
-        HIP_CHECK(launch_ts_mux(p, (uint32_t)std::max(x->num_cus * 8, 1), x->stream));
-        HIP_CHECK(hist_mark(x, 6, 1));
-        {
-            Readback rb(x);
-            HIP_CHECK(rb.add(&pl, x->d_ts_fixed, sizeof(pl)));
-            HIP_CHECK(rb.run());
-        }
+        if (int rc = mux_launch(x, 6, launch_ts_mux, p, &pl)) return rc;
         if (pl.commit) break;
         result->bytes = pl.bytes;
-        if (pl.bytes > out_cap || attempt || device_out)
+        if (pl.bytes > out_cap || attempt || m.device_out)
             return fail(EDGPU_OUT_OVERFLOW, "transport-stream mux: " + std::to_string(pl.bytes) + " bytes needed; nothing was written");
         // the caller has room, the context's staging did not: grown, and the mux made again
-        HIP_CHECK(x->d_ts_out.reserve(pl.bytes, x->stream));
+        HIP_CHECK(x->mux.out.reserve(pl.bytes, x->stream));
     }
     result->bytes = pl.bytes;
     Readback rb(x);
-    if (!device_out) HIP_CHECK(rb.add(out, x->d_ts_out.ptr, pl.bytes));
+    if (!m.device_out) HIP_CHECK(rb.add(out, x->mux.out.ptr, pl.bytes));
     HIP_CHECK(rb.add(ts_units, x->d_ts_rows.ptr, (size_t)n_units * sizeof(edgpu_ts_unit)));
     HIP_CHECK(rb.add(states, x->d_ts_states.ptr + n_streams, (size_t)n_streams * sizeof(edgpu_ts_state)));
     HIP_CHECK(rb.run());
@@ -2747,118 +2840,61 @@ int edgpu_mp4_mux(edgpu_ctx* x, const edgpu_mp4_config* cfg, const void* es, uin
                   const edgpu_tap_unit* units, uint32_t n_units, const edgpu_tap_stream* streams, uint32_t n_streams,
                   edgpu_mp4_state* states, void* out, uint64_t out_cap, int out_kind, edgpu_mp4_sample* samples,
                   edgpu_mp4_frag* frags, uint32_t frag_cap, edgpu_mp4_result* result) {
-    if (!x || !result || (!es && es_bytes) || (!out && out_cap) || (!units && n_units) || (!samples && n_units) ||
-        (!streams && n_streams) || (!states && n_streams) || (!frags && frag_cap))
-        return fail(EDGPU_BAD_ARGUMENT, "bad argument");
-    for (int k : {es_kind, out_kind})
-        if (k != EDGPU_PTR_HOST && k != EDGPU_PTR_DEVICE && k != EDGPU_PTR_PINNED) return fail(EDGPU_BAD_ARGUMENT, "bad pointer kind");
-    const bool device_es = es_kind == EDGPU_PTR_DEVICE, device_out = out_kind == EDGPU_PTR_DEVICE;
-    if ((device_es && ((uintptr_t)es & 15)) || (device_out && ((uintptr_t)out & 15)))
-        return fail(EDGPU_BAD_ARGUMENT, "device `es` and `out` must be 16-B aligned");
+    if (!frags && frag_cap) return fail(EDGPU_BAD_ARGUMENT, "bad argument");
+    MuxCall m;
+    if (int rc = mux_args(&m, x, result, es, es_bytes, es_kind, units, n_units, streams, n_streams, states, out, out_cap, out_kind, samples))
+        return rc;
     edgpu_mp4_config c;
     memset(&c, 0, sizeof(c));
     if (cfg) c = *cfg;
     if (!c.default_duration) c.default_duration = 3600;
     if (c.flags) return fail(EDGPU_BAD_ARGUMENT, "bad fragmented-MP4 configuration: no flags are defined");
-    // the rows the kernels index by: checked here, on the host
-    for (uint32_t i = 0; i < n_units; i++) {
-        if (units[i].stream >= n_streams) return fail(EDGPU_BAD_ARGUMENT, "a unit's stream index is out of range");
-        if (units[i].offset > es_bytes || units[i].bytes > es_bytes - units[i].offset)
-            return fail(EDGPU_BAD_ARGUMENT, "a unit reaches outside the ES bytes");
-    }
-    std::vector<Mp4Range> ranges(n_streams);
-    uint64_t covered = 0, next = 0, most = 0;       // `most`: the bytes the output can need at the most
+    std::vector<Mp4Range> ranges;
+    std::vector<uint64_t> totals;
+    uint64_t covered, most = 0, slot = 0;           // `most`: the bytes the output can need at the most
+    if (int rc = mux_check_rows(m, &ranges, &covered, &totals)) return rc;
     for (uint32_t s = 0; s < n_streams; s++) {
-        const uint64_t first = streams[s].unit_first, count = streams[s].unit_count;
-        if (first + count > n_units) return fail(EDGPU_BAD_ARGUMENT, "a stream's unit range reaches outside the units");
-        if (count) {
-            if (first < next) return fail(EDGPU_BAD_ARGUMENT, "the streams' unit ranges must ascend without overlap");
-            next = first + count;
-        }
-        uint64_t total = 0;
-        for (uint64_t i = first; i < first + count; i++) total += units[i].bytes;
-        if (total >= (1ull << 31)) return fail(EDGPU_BAD_ARGUMENT, "a stream's units total 2^31 bytes or more");
-        if (total + 108 * count >= (1ull << 32))   // fragment sizes and offsets within a run are 32-bit
+        const uint64_t count = ranges[s].count;
+        if (totals[s] >= (1ull << 31)) return fail(EDGPU_BAD_ARGUMENT, "a stream's units total 2^31 bytes or more");
+        if (totals[s] + 108 * count >= (1ull << 32))   // fragment sizes and offsets within a run are 32-bit
             return fail(EDGPU_BAD_ARGUMENT, "a stream's run could reach 2^32 bytes");
-        ranges[s] = Mp4Range{(uint32_t)first, (uint32_t)count, (uint32_t)(covered + s), 0u};
-        covered += count;
-        most += total + 108 * count + 16;
+        ranges[s].slot = (uint32_t)slot;            // a row holds count + 1 Mp4FragRecs
+        slot += count + 1;
+        most += totals[s] + 108 * count + 16;
     }
-    memset(result, 0, sizeof(*result));
-    result->units = n_units; result->streams = n_streams;
-    if (!n_streams) {
-        if (n_units) memset(samples, 0, (size_t)n_units * sizeof(edgpu_mp4_sample));
-        return EDGPU_OK;
-    }
+    if (mux_no_streams(m, result, samples)) return EDGPU_OK;
     DEVICE_ENTER(x);
-    if (!x->hist[7][0][0])
-        for (auto& s : x->hist[7]) for (auto& e : s) HIP_CHECK(hipEventCreate(&e));
     if (!x->d_mp4_place && dmalloc(&x->d_mp4_place, sizeof(Mp4Place)) != hipSuccess)
         return fail(EDGPU_OUT_OF_MEMORY, "fragmented-MP4 mux staging");
-    const uint64_t nwords = (es_bytes + 31) / 32, nchunks = (nwords + kMp4ChunkWords - 1) / kMp4ChunkWords;
     const size_t nu = std::max<uint32_t>(n_units, 1);
-    HIP_CHECK(x->d_mp4_units_in.reserve(nu, x->stream));
-    HIP_CHECK(x->d_mp4_recs.reserve(nu, x->stream));
     HIP_CHECK(x->d_mp4_samps.reserve(nu, x->stream));
     HIP_CHECK(x->d_mp4_rows.reserve(nu, x->stream));
     HIP_CHECK(x->d_mp4_frags.reserve(nu, x->stream));
     HIP_CHECK(x->d_mp4_frecs.reserve((size_t)n_units + n_streams, x->stream));
-    HIP_CHECK(x->d_mp4_ranges.reserve(n_streams, x->stream));
     HIP_CHECK(x->d_mp4_srecs.reserve(n_streams, x->stream));
-    HIP_CHECK(x->d_mp4_states.reserve(2 * (size_t)n_streams, x->stream));
-    HIP_CHECK(x->d_mp4_bitmap.reserve(nwords + 1, x->stream));
-    HIP_CHECK(x->d_mp4_chunks.reserve(nchunks + 1, x->stream));
-    HIP_CHECK(x->d_mp4_lens.reserve(es_bytes / 4 + 1, x->stream));
-    if (!device_es) HIP_CHECK(x->d_mp4_es.reserve(es_bytes + 16, x->stream));
-    // staging for the most the units can need, so the verdict never depends on the staging
-    if (!device_out) HIP_CHECK(x->d_mp4_out.reserve(std::max<uint64_t>(std::min<uint64_t>(out_cap, most), 16), x->stream));
-    if (n_units) HIP_CHECK(hipMemcpyAsync(x->d_mp4_units_in.ptr, units, (size_t)n_units * sizeof(edgpu_tap_unit), hipMemcpyHostToDevice, x->stream));
-    HIP_CHECK(hipMemcpyAsync(x->d_mp4_ranges.ptr, ranges.data(), (size_t)n_streams * sizeof(Mp4Range), hipMemcpyHostToDevice, x->stream));
-    HIP_CHECK(hipMemcpyAsync(x->d_mp4_states.ptr, states, (size_t)n_streams * sizeof(edgpu_mp4_state), hipMemcpyHostToDevice, x->stream));
-    if (!device_es && es_bytes) HIP_CHECK(hipMemcpyAsync(x->d_mp4_es.ptr, es, es_bytes, hipMemcpyHostToDevice, x->stream));
-    if (covered != n_units) HIP_CHECK(hipMemsetAsync(x->d_mp4_recs.ptr, 0, (size_t)n_units * sizeof(Mp4Rec), x->stream));
-    HIP_CHECK(wsync(x, x->stream));             // `ranges` is on the stack
     Mp4Params p;
-    p.sc.es = device_es ? (const uint8_t*)es : x->d_mp4_es.ptr;
-    p.sc.es_bytes = es_bytes;
-    p.units = x->d_mp4_units_in.ptr; p.ranges = x->d_mp4_ranges.ptr;
+    // staging for the most the units can need, so the verdict never depends on the staging
+    if (int rc = mux_upload(x, m, std::max<uint64_t>(std::min(out_cap, most), 16), &p.sc, ranges, x->d_mp4_ranges, states, x->d_mp4_states,
+                            x->d_mp4_recs, covered))
+        return rc;
+    p.units = x->mux.units.ptr; p.ranges = x->d_mp4_ranges.ptr;
     p.states = x->d_mp4_states.ptr; p.new_states = x->d_mp4_states.ptr + n_streams;
-    p.sc.bitmap = x->d_mp4_bitmap.ptr; p.sc.chunk_first = x->d_mp4_chunks.ptr; p.sc.lens = x->d_mp4_lens.ptr;
-    p.sc.nwords = nwords; p.sc.nchunks = nchunks;
     p.recs = x->d_mp4_recs.ptr; p.frecs = x->d_mp4_frecs.ptr; p.srecs = x->d_mp4_srecs.ptr; p.samps = x->d_mp4_samps.ptr;
     p.place = x->d_mp4_place;
-    p.out = device_out ? (uint8_t*)out : x->d_mp4_out.ptr;
+    p.out = m.device_out ? (uint8_t*)out : x->mux.out.ptr;
     p.rows = x->d_mp4_rows.ptr; p.frags = x->d_mp4_frags.ptr;
     p.out_cap = out_cap;
     p.time_offset = c.time_offset;
     p.frag_cap = frag_cap; p.n_units = n_units; p.n_streams = n_streams; p.n_slots = n_units + n_streams;
     p.max_samples = c.max_samples; p.default_duration = c.default_duration;
-    HIP_CHECK(hist_mark(x, 7, 0));
-    HIP_CHECK(launch_mp4_mux(p, (uint32_t)std::max(x->num_cus * 8, 1), x->stream));
-    HIP_CHECK(hist_mark(x, 7, 1));
     Mp4Place pl;
-    {
-        Readback rb(x);
-        HIP_CHECK(rb.add(&pl, x->d_mp4_place, sizeof(pl)));
-        HIP_CHECK(rb.run());
-    }
+    if (int rc = mux_launch(x, 7, launch_mp4_mux, p, &pl)) return rc;
     result->bytes = pl.bytes; result->frags = pl.frags;
     if (!pl.commit)
         return fail(EDGPU_OUT_OVERFLOW, "fragmented-MP4 mux: " + std::to_string(pl.bytes) + " bytes and " + std::to_string(pl.frags) +
                                         " fragment rows needed; nothing was written");
-    std::vector<Mp4StreamRec> runs;
-    if (!device_out) {                          // the bytes between two runs are not the caller's to lose
-        runs.resize(n_streams);
-        Readback rr(x);
-        HIP_CHECK(rr.add(runs.data(), x->d_mp4_srecs.ptr, (size_t)n_streams * sizeof(Mp4StreamRec)));
-        HIP_CHECK(rr.run());
-    }
     Readback rb(x);
-    for (size_t s = 0; s < runs.size();) {
-        uint64_t a = runs[s].base, b = a + runs[s].bytes;
-        for (s++; s < runs.size() && runs[s].base == b; s++) b += runs[s].bytes;   // runs that touch: one copy
-        if (b > a) HIP_CHECK(rb.add((uint8_t*)out + a, x->d_mp4_out.ptr + a, b - a));
-    }
+    if (int rc = mux_read_runs(x, m, x->d_mp4_srecs.ptr, sizeof(Mp4StreamRec), rb)) return rc;
     HIP_CHECK(rb.add(samples, x->d_mp4_rows.ptr, (size_t)n_units * sizeof(edgpu_mp4_sample)));
     HIP_CHECK(rb.add(frags, x->d_mp4_frags.ptr, (size_t)pl.frags * sizeof(edgpu_mp4_frag)));
     HIP_CHECK(rb.add(states, x->d_mp4_states.ptr + n_streams, (size_t)n_streams * sizeof(edgpu_mp4_state)));
@@ -2871,112 +2907,51 @@ int edgpu_flv_mux(edgpu_ctx* x, const edgpu_flv_config* cfg, const void* es, uin
                   const edgpu_tap_unit* units, uint32_t n_units, const edgpu_tap_stream* streams, uint32_t n_streams,
                   edgpu_flv_state* states, void* out, uint64_t out_cap, int out_kind, edgpu_flv_tag* tags,
                   edgpu_flv_result* result) {
-    if (!x || !result || (!es && es_bytes) || (!out && out_cap) || (!units && n_units) || (!tags && n_units) ||
-        (!streams && n_streams) || (!states && n_streams))
-        return fail(EDGPU_BAD_ARGUMENT, "bad argument");
-    for (int k : {es_kind, out_kind})
-        if (k != EDGPU_PTR_HOST && k != EDGPU_PTR_DEVICE && k != EDGPU_PTR_PINNED) return fail(EDGPU_BAD_ARGUMENT, "bad pointer kind");
-    const bool device_es = es_kind == EDGPU_PTR_DEVICE, device_out = out_kind == EDGPU_PTR_DEVICE;
-    if ((device_es && ((uintptr_t)es & 15)) || (device_out && ((uintptr_t)out & 15)))
-        return fail(EDGPU_BAD_ARGUMENT, "device `es` and `out` must be 16-B aligned");
+    MuxCall m;
+    if (int rc = mux_args(&m, x, result, es, es_bytes, es_kind, units, n_units, streams, n_streams, states, out, out_cap, out_kind, tags))
+        return rc;
     edgpu_flv_config c;
     memset(&c, 0, sizeof(c));
     if (cfg) c = *cfg;
     if (c.flags) return fail(EDGPU_BAD_ARGUMENT, "bad FLV configuration: no flags are defined");
-    // the rows the kernels index by: checked here, on the host
-    for (uint32_t i = 0; i < n_units; i++) {
-        if (units[i].stream >= n_streams) return fail(EDGPU_BAD_ARGUMENT, "a unit's stream index is out of range");
-        if (units[i].offset > es_bytes || units[i].bytes > es_bytes - units[i].offset)
-            return fail(EDGPU_BAD_ARGUMENT, "a unit reaches outside the ES bytes");
+    std::vector<FlvRange> ranges;
+    std::vector<uint64_t> totals;
+    uint64_t covered, most = 0;                     // `most`: the bytes the output can need at the most
+    if (int rc = mux_check_rows(m, &ranges, &covered, &totals)) return rc;
+    for (uint32_t i = 0; i < n_units; i++)
         if (units[i].bytes > 0xFFFFFAu) return fail(EDGPU_BAD_ARGUMENT, "a unit of more than 0xFFFFFA bytes: an FLV tag's DataSize is 24 bits");
-    }
-    std::vector<FlvRange> ranges(n_streams);
-    uint64_t covered = 0, next = 0, most = 0;       // `most`: the bytes the output can need at the most
     for (uint32_t s = 0; s < n_streams; s++) {
-        const uint64_t first = streams[s].unit_first, count = streams[s].unit_count;
-        if (first + count > n_units) return fail(EDGPU_BAD_ARGUMENT, "a stream's unit range reaches outside the units");
-        if (count) {
-            if (first < next) return fail(EDGPU_BAD_ARGUMENT, "the streams' unit ranges must ascend without overlap");
-            next = first + count;
-        }
-        uint64_t total = 0;
-        for (uint64_t i = first; i < first + count; i++) total += units[i].bytes;
-        if (total + 20 * count >= (1ull << 32))     // offsets within a run are 32-bit
+        if (totals[s] + 20ull * ranges[s].count >= (1ull << 32))    // offsets within a run are 32-bit
             return fail(EDGPU_BAD_ARGUMENT, "a stream's run could reach 2^32 bytes");
-        ranges[s] = FlvRange{(uint32_t)first, (uint32_t)count};
-        covered += count;
-        most += total + 20 * count + 16;
+        most += totals[s] + 20ull * ranges[s].count + 16;
     }
-    memset(result, 0, sizeof(*result));
-    result->units = n_units; result->streams = n_streams;
-    if (!n_streams) {
-        if (n_units) memset(tags, 0, (size_t)n_units * sizeof(edgpu_flv_tag));
-        return EDGPU_OK;
-    }
+    if (mux_no_streams(m, result, tags)) return EDGPU_OK;
     DEVICE_ENTER(x);
-    if (!x->hist[8][0][0])
-        for (auto& s : x->hist[8]) for (auto& e : s) HIP_CHECK(hipEventCreate(&e));
     if (!x->d_flv_place && dmalloc(&x->d_flv_place, sizeof(FlvPlace)) != hipSuccess)
         return fail(EDGPU_OUT_OF_MEMORY, "FLV mux staging");
-    const uint64_t nwords = (es_bytes + 31) / 32, nchunks = (nwords + kScodeChunkWords - 1) / kScodeChunkWords;
-    const size_t nu = std::max<uint32_t>(n_units, 1);
-    HIP_CHECK(x->d_flv_units_in.reserve(nu, x->stream));
-    HIP_CHECK(x->d_flv_recs.reserve(nu, x->stream));
-    HIP_CHECK(x->d_flv_rows.reserve(nu, x->stream));
-    HIP_CHECK(x->d_flv_ranges.reserve(n_streams, x->stream));
+    HIP_CHECK(x->d_flv_rows.reserve(std::max<uint32_t>(n_units, 1), x->stream));
     HIP_CHECK(x->d_flv_srecs.reserve(n_streams, x->stream));
-    HIP_CHECK(x->d_flv_states.reserve(2 * (size_t)n_streams, x->stream));
-    HIP_CHECK(x->d_flv_bitmap.reserve(nwords + 1, x->stream));
-    HIP_CHECK(x->d_flv_chunks.reserve(nchunks + 1, x->stream));
-    HIP_CHECK(x->d_flv_lens.reserve(es_bytes / 4 + 1, x->stream));
-    if (!device_es) HIP_CHECK(x->d_flv_es.reserve(es_bytes + 16, x->stream));
-    // staging for the most the units can need, so the verdict never depends on the staging
-    if (!device_out) HIP_CHECK(x->d_flv_out.reserve(std::max<uint64_t>(std::min<uint64_t>(out_cap, most), 16), x->stream));
-    if (n_units) HIP_CHECK(hipMemcpyAsync(x->d_flv_units_in.ptr, units, (size_t)n_units * sizeof(edgpu_tap_unit), hipMemcpyHostToDevice, x->stream));
-    HIP_CHECK(hipMemcpyAsync(x->d_flv_ranges.ptr, ranges.data(), (size_t)n_streams * sizeof(FlvRange), hipMemcpyHostToDevice, x->stream));
-    HIP_CHECK(hipMemcpyAsync(x->d_flv_states.ptr, states, (size_t)n_streams * sizeof(edgpu_flv_state), hipMemcpyHostToDevice, x->stream));
-    if (!device_es && es_bytes) HIP_CHECK(hipMemcpyAsync(x->d_flv_es.ptr, es, es_bytes, hipMemcpyHostToDevice, x->stream));
-    if (covered != n_units) HIP_CHECK(hipMemsetAsync(x->d_flv_recs.ptr, 0, (size_t)n_units * sizeof(FlvRec), x->stream));
-    HIP_CHECK(wsync(x, x->stream));             // `ranges` is on the stack
     FlvParams p;
-    p.sc.es = device_es ? (const uint8_t*)es : x->d_flv_es.ptr;
-    p.sc.es_bytes = es_bytes;
-    p.sc.bitmap = x->d_flv_bitmap.ptr; p.sc.chunk_first = x->d_flv_chunks.ptr; p.sc.lens = x->d_flv_lens.ptr;
-    p.sc.nwords = nwords; p.sc.nchunks = nchunks;
-    p.units = x->d_flv_units_in.ptr; p.ranges = x->d_flv_ranges.ptr;
+    // staging for the most the units can need, so the verdict never depends on the staging
+    if (int rc = mux_upload(x, m, std::max<uint64_t>(std::min(out_cap, most), 16), &p.sc, ranges, x->d_flv_ranges, states, x->d_flv_states,
+                            x->d_flv_recs, covered))
+        return rc;
+    p.units = x->mux.units.ptr; p.ranges = x->d_flv_ranges.ptr;
     p.states = x->d_flv_states.ptr; p.new_states = x->d_flv_states.ptr + n_streams;
     p.recs = x->d_flv_recs.ptr; p.srecs = x->d_flv_srecs.ptr;
     p.place = x->d_flv_place;
-    p.out = device_out ? (uint8_t*)out : x->d_flv_out.ptr;
+    p.out = m.device_out ? (uint8_t*)out : x->mux.out.ptr;
     p.rows = x->d_flv_rows.ptr;
     p.out_cap = out_cap;
     p.time_offset = c.time_offset;
     p.n_units = n_units; p.n_streams = n_streams;
-    HIP_CHECK(hist_mark(x, 8, 0));
-    HIP_CHECK(launch_flv_mux(p, (uint32_t)std::max(x->num_cus * 8, 1), x->stream));
-    HIP_CHECK(hist_mark(x, 8, 1));
     FlvPlace pl;
-    {
-        Readback rb(x);
-        HIP_CHECK(rb.add(&pl, x->d_flv_place, sizeof(pl)));
-        HIP_CHECK(rb.run());
-    }
+    if (int rc = mux_launch(x, 8, launch_flv_mux, p, &pl)) return rc;
     result->bytes = pl.bytes;
     if (!pl.commit)
         return fail(EDGPU_OUT_OVERFLOW, "FLV mux: " + std::to_string(pl.bytes) + " bytes needed; nothing was written");
-    std::vector<FlvStreamRec> runs;
-    if (!device_out) {                          // the bytes between two runs are not the caller's to lose
-        runs.resize(n_streams);
-        Readback rr(x);
-        HIP_CHECK(rr.add(runs.data(), x->d_flv_srecs.ptr, (size_t)n_streams * sizeof(FlvStreamRec)));
-        HIP_CHECK(rr.run());
-    }
     Readback rb(x);
-    for (size_t s = 0; s < runs.size();) {
-        uint64_t a = runs[s].base, b = a + runs[s].bytes;
-        for (s++; s < runs.size() && runs[s].base == b; s++) b += runs[s].bytes;   // runs that touch: one copy
-        if (b > a) HIP_CHECK(rb.add((uint8_t*)out + a, x->d_flv_out.ptr + a, b - a));
-    }
+    if (int rc = mux_read_runs(x, m, x->d_flv_srecs.ptr, sizeof(FlvStreamRec), rb)) return rc;
     HIP_CHECK(rb.add(tags, x->d_flv_rows.ptr, (size_t)n_units * sizeof(edgpu_flv_tag)));
     HIP_CHECK(rb.add(states, x->d_flv_states.ptr + n_streams, (size_t)n_streams * sizeof(edgpu_flv_state)));
     HIP_CHECK(rb.run());

@@ -148,17 +148,13 @@ __global__ __launch_bounds__(256) void k_flv_place(FlvParams P) {
     uint64_t cb = 0;
     for (uint32_t b = 0; b < P.n_streams; b += kFlvPlaceThreads) {
         const uint32_t i = b + t;
-        const uint64_t bytes = i < P.n_streams ? P.srecs[i].bytes : 0ull;
-        const uint64_t vb = (bytes + 15) & ~15ull;
         uint64_t tb;
-        const uint64_t base = cb + block_exclusive_scan<uint64_t>(vb, scratch, tb);
+        const uint64_t base = cb + place_round(P.srecs, P.n_streams, i, scratch, tb);
         if (i < P.n_streams) P.srecs[i].base = base;
         cb += tb;
     }
     if (t == 0) {
-        // the last run is not padded: its base + bytes is the sum of every run less the last one's padding
-        const uint64_t last = P.n_streams ? P.srecs[P.n_streams - 1].bytes : 0ull;
-        const uint64_t total = cb - (((last + 15) & ~15ull) - last);
+        const uint64_t total = place_total(P.srecs, P.n_streams, cb);
         FlvPlace pl;
         pl.bytes = total;
         pl.commit = total <= P.out_cap ? 1u : 0u;
@@ -215,11 +211,7 @@ __global__ __launch_bounds__(256) void k_flv_pack(FlvParams P) {
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t w = gid; w < nwords; w += nthreads) {
         const uint64_t o = w << 4;
-        uint32_t lo = 0, hi = P.n_streams;                  // srecs[lo].base <= o < srecs[hi].base
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (P.srecs[mid].base <= o) lo = mid; else hi = mid;
-        }
+        const uint32_t lo = run_of_byte(P.srecs, P.n_streams, o);
         const FlvStreamRec sr = P.srecs[lo];
         const uint64_t rel64 = o - sr.base;
         if (rel64 >= sr.bytes) continue;
@@ -236,12 +228,7 @@ __global__ __launch_bounds__(256) void k_flv_pack(FlvParams P) {
         if (x >= kFlvHead && x + 16 <= kFlvHead + c.bytes) {
             const uint64_t sp = c.src + (x - kFlvHead);
             if (scode_clear16(P.sc, sp)) {
-                const uintptr_t a = (uintptr_t)(P.sc.es + sp);
-                const uint32_t sh = (uint32_t)(a & 15u);
-                const u32x4* sw = reinterpret_cast<const u32x4*>(a & ~(uintptr_t)15);
-                const u32x4 l = sw[0];
-                const u32x4 h = sh ? sw[1] : l;
-                *reinterpret_cast<u32x4*>(P.out + o) = funnel16(l, h, sh);
+                *reinterpret_cast<u32x4*>(P.out + o) = load16_funnel(P.sc.es + sp);
                 continue;
             }
         }

@@ -191,11 +191,9 @@ __global__ __launch_bounds__(256) void k_mp4_place(Mp4Params P) {
     uint64_t cb = 0, cf = 0;
     for (uint32_t b = 0; b < P.n_streams; b += kMp4PlaceThreads) {
         const uint32_t i = b + t;
-        const uint64_t bytes = i < P.n_streams ? P.srecs[i].bytes : 0ull;
-        const uint64_t vb = (bytes + 15) & ~15ull;
         const uint64_t vf = i < P.n_streams ? P.srecs[i].nfrags : 0ull;
         uint64_t tb, tf;
-        const uint64_t base = cb + block_exclusive_scan<uint64_t>(vb, scratch, tb);
+        const uint64_t base = cb + place_round(P.srecs, P.n_streams, i, scratch, tb);
         const uint64_t fbase = cf + block_exclusive_scan<uint64_t>(vf, scratch, tf);
         if (i < P.n_streams) {
             P.srecs[i].base = base;
@@ -205,9 +203,7 @@ __global__ __launch_bounds__(256) void k_mp4_place(Mp4Params P) {
         cf += tf;
     }
     if (t == 0) {
-        // the last run is not padded: its base + bytes is the sum of every run less the last one's padding
-        const uint64_t last = P.n_streams ? P.srecs[P.n_streams - 1].bytes : 0ull;
-        const uint64_t total = cb - (((last + 15) & ~15ull) - last);
+        const uint64_t total = place_total(P.srecs, P.n_streams, cb);
         Mp4Place pl;
         pl.bytes = total;
         pl.frags = cf > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cf;
@@ -373,11 +369,7 @@ __global__ __launch_bounds__(256) void k_mp4_pack(Mp4Params P) {
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t w = gid; w < nwords; w += nthreads) {
         const uint64_t o = w << 4;
-        uint32_t lo = 0, hi = P.n_streams;                  // srecs[lo].base <= o < srecs[hi].base
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (P.srecs[mid].base <= o) lo = mid; else hi = mid;
-        }
+        const uint32_t lo = run_of_byte(P.srecs, P.n_streams, o);
         const Mp4StreamRec sr = P.srecs[lo];
         const uint64_t rel = o - sr.base;
         if (rel >= sr.bytes) continue;
@@ -396,12 +388,7 @@ __global__ __launch_bounds__(256) void k_mp4_pack(Mp4Params P) {
             if (t + 16 <= c.s_bytes) {
                 const uint64_t sp = c.s_src + t;
                 if (scode_clear16(P.sc, sp)) {
-                    const uintptr_t a = (uintptr_t)(P.sc.es + sp);
-                    const uint32_t sh = (uint32_t)(a & 15u);
-                    const u32x4* sw = reinterpret_cast<const u32x4*>(a & ~(uintptr_t)15);
-                    const u32x4 l = sw[0];
-                    const u32x4 h = sh ? sw[1] : l;
-                    *reinterpret_cast<u32x4*>(P.out + o) = funnel16(l, h, sh);
+                    *reinterpret_cast<u32x4*>(P.out + o) = load16_funnel(P.sc.es + sp);
                     continue;
                 }
             }

@@ -281,7 +281,6 @@ struct ScodeView {
 // k_mp4_place (one workgroup), k_mp4_rows (flat over fragments and units) and k_mp4_pack (flat over
 // the output's 16-B words).
 constexpr uint32_t kMp4None = 0xFFFFFFFFu;
-constexpr uint32_t kMp4ChunkWords = kScodeChunkWords;
 struct Mp4Range { uint32_t first, count, slot, _pad; };   // slot: the row's first Mp4FragRec (the rows before it hold count + 1 each)
 struct Mp4Rec {                 // per unit, from k_mp4_plan; zero for a unit no row covers
     uint64_t dts;

@@ -1,6 +1,7 @@
 // edgpu_scode.h -- the start codes of an Annex-B elementary stream, shared by the muxers that turn
 // them into NAL lengths (edgpu_mp4.hip, edgpu_flv.hip; device code): the bitmap of every 00 00 00 01
-// and the table of the distance from each to the next, and the reads both muxers make of them.
+// and the table of the distance from each to the next, the reads both muxers make of them, and (at
+// the end) the pieces their pack and placement kernels have in common.
 //
 //   scode_mark     flat over the ES, a lane per 32 bytes (two aligned 16-B loads and the dword after
 //                  them): one word of the bitmap -- bit b of word w says 00 00 00 01 begins at ES byte
@@ -131,6 +132,47 @@ __device__ __forceinline__ uint32_t scode_sample_byte(const ScodeView& V, uint64
         return (len >> (8 * (3 - j))) & 0xFFu;
     }
     return V.es[sp];
+}
+
+// ---- What k_mp4_pack / k_flv_pack and k_mp4_place / k_flv_place share.  SRec is the mux's stream
+// record: `bytes` and `base` of the stream's run in the output; runs begin 16-B aligned. ----
+
+// The run that holds output byte `o`: srecs[lo].base <= o < srecs[lo + 1].base
+template <typename SRec>
+__device__ __forceinline__ uint32_t run_of_byte(const SRec* srecs, uint32_t n_streams, uint64_t o) {
+    uint32_t lo = 0, hi = n_streams;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (srecs[mid].base <= o) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// The 16 bytes at `src`, of any alignment: two aligned 16-B loads, funnelled.  The pack's fast path
+// for a word inside one sample that scode_clear16 passes: one aligned 16-B store of this.
+__device__ __forceinline__ u32x4 load16_funnel(const uint8_t* src) {
+    const uintptr_t a = (uintptr_t)src;
+    const uint32_t sh = (uint32_t)(a & 15u);
+    const u32x4* sw = reinterpret_cast<const u32x4*>(a & ~(uintptr_t)15);
+    const u32x4 l = sw[0];
+    const u32x4 h = sh ? sw[1] : l;
+    return funnel16(l, h, sh);
+}
+
+// One round of the placement scan (every thread of the workgroup, stream `i` each): the aligned
+// bytes of the round's runs before stream i's; `round_total`: of all the round's runs
+template <typename SRec>
+__device__ __forceinline__ uint64_t place_round(const SRec* srecs, uint32_t n_streams, uint32_t i, uint64_t* scratch, uint64_t& round_total) {
+    const uint64_t bytes = i < n_streams ? srecs[i].bytes : 0ull;
+    return block_exclusive_scan<uint64_t>((bytes + 15) & ~15ull, scratch, round_total);
+}
+
+// The output's bytes from the rounds' sum `cb`.  The last run is not padded: its base + bytes is the
+// sum of every run less the last one's padding
+template <typename SRec>
+__device__ __forceinline__ uint64_t place_total(const SRec* srecs, uint32_t n_streams, uint64_t cb) {
+    const uint64_t last = n_streams ? srecs[n_streams - 1].bytes : 0ull;
+    return cb - (((last + 15) & ~15ull) - last);
 }
 
 }  // namespace edgpu

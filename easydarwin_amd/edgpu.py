@@ -515,6 +515,11 @@ class Context:
         self.lib = lib
         self.device = int(device)
         self._ntracks = {}          # session -> tracks (senders_of without a C call per session)
+        # tap_drain_ts / _mp4 / _flv: one device ES buffer for all; per format the mux's state rows
+        # by (session, track) and the host output's size
+        self._mux_es = None
+        self._mux_states = {"ts": {}, "mp4": {}, "flv": {}}
+        self._mux_caps = {}
 
     def close(self):
         if self.h:
@@ -548,12 +553,9 @@ class Context:
         down with it (kill_clients_when_broadcast_stops)."""
         _check(self.lib.edgpu_session_remove(self.h, session, SESSION_KILL_OUTPUTS if kill_outputs else 0))
         self._ntracks.pop(session, None)
-        for k in [k for k in getattr(self, "_ts_states", {}) if k[0] == session]:
-            del self._ts_states[k]
-        for k in [k for k in getattr(self, "_mp4_states", {}) if k[0] == session]:
-            del self._mp4_states[k]
-        for k in [k for k in getattr(self, "_flv_states", {}) if k[0] == session]:
-            del self._flv_states[k]
+        for kept in self._mux_states.values():
+            for k in [k for k in kept if k[0] == session]:
+                del kept[k]
 
     def subscriber_add(self, session: int, transport: int = TRANSPORT_UDP) -> int:
         out = C.c_uint32()
@@ -746,9 +748,8 @@ class Context:
 
     def tap_disable(self, session: int, track: int):
         _check(self.lib.edgpu_tap_disable(self.h, session, track))
-        getattr(self, "_ts_states", {}).pop((session, track), None)
-        getattr(self, "_mp4_states", {}).pop((session, track), None)
-        getattr(self, "_flv_states", {}).pop((session, track), None)
+        for kept in self._mux_states.values():
+            kept.pop((session, track), None)
 
     def tap_drain_raw(self, flags, out_ptr, out_cap, ptr_kind, units: np.ndarray, streams: np.ndarray) -> tuple:
         """edgpu_tap_drain as it is: (status, TapResult)."""
@@ -800,43 +801,52 @@ class Context:
         of 188-byte packets, TS_UNIT_DTYPE rows (one per drained unit) and the drain's
         TAP_STREAM_DTYPE rows.  The mux's state rows are kept here by (session, track); tap_disable
         and session_remove drop them."""
-        if not hasattr(self, "_ts_states"):
-            self._ts_states = {}
-        if getattr(self, "_ts_es", None) is None:
-            self._ts_es = self.device_alloc(1 << 20)
+        out, _, (ts_units,), _, streams = self._drain_and_mux(
+            "ts", self.ts_mux_raw, TS_STATE_DTYPE, lambda n: (np.zeros(n, dtype=TS_UNIT_DTYPE),), flush, cfg)
+        return out, ts_units, streams
+
+    def _drain_and_mux(self, fmt, mux_raw, state_dtype, new_rows, flush, cfg):
+        """What tap_drain_ts, tap_drain_mp4 and tap_drain_flv share: the drain into the device ES
+        buffer (grown, and the drain made again, on overflow), the state rows from those kept by
+        (session, track), `mux_raw` into a host array (grown likewise) and the new states kept.
+        `new_rows(n_units)` makes the format's row arrays, the last arguments of `mux_raw`.  Returns
+        (bytes, the mux's result, rows, units, streams)."""
+        if self._mux_es is None:
+            self._mux_es = self.device_alloc(1 << 20)
         caps = getattr(self, "_tap_caps", [1 << 20, 4096, 64])
         for attempt in range(2):
             units = np.zeros(caps[1], dtype=TAP_UNIT_DTYPE)
             streams = np.zeros(caps[2], dtype=TAP_STREAM_DTYPE)
-            rc, res = self.tap_drain_raw(TAP_FLUSH if flush else 0, self._ts_es.ptr, self._ts_es.nbytes, PTR_DEVICE, units, streams)
+            rc, res = self.tap_drain_raw(TAP_FLUSH if flush else 0, self._mux_es.ptr, self._mux_es.nbytes, PTR_DEVICE, units, streams)
             if rc != OUT_OVERFLOW or attempt:
                 break
             caps = [caps[0], max(caps[1], int(res.units)), max(caps[2], int(res.streams))]
             self._tap_caps = caps
-            if res.bytes > self._ts_es.nbytes:
-                self._ts_es.free()
-                self._ts_es = None
-                self._ts_es = self.device_alloc(max(int(res.bytes), 2 * caps[0]))
+            if res.bytes > self._mux_es.nbytes:
+                self._mux_es.free()
+                self._mux_es = None
+                self._mux_es = self.device_alloc(max(int(res.bytes), 2 * caps[0]))
         _check(rc)
         units, streams = units[:res.units], streams[:res.streams]
         keys = [(int(st["session"]), int(st["track"])) for st in streams]
-        states = np.zeros(len(streams), dtype=TS_STATE_DTYPE)
+        kept = self._mux_states[fmt]
+        states = np.zeros(len(streams), dtype=state_dtype)
         for i, k in enumerate(keys):
-            if k in self._ts_states:
-                states[i] = self._ts_states[k]
-        ts_units = np.zeros(len(units), dtype=TS_UNIT_DTYPE)
-        cap = getattr(self, "_ts_cap", 1 << 20)
+            if k in kept:
+                states[i] = kept[k]
+        rows = new_rows(len(units))
+        cap = self._mux_caps.get(fmt, 1 << 20)
         for attempt in range(2):
             out = np.empty(cap, dtype=np.uint8)
-            rc, tres = self.ts_mux_raw(cfg, self._ts_es.ptr, int(res.bytes), PTR_DEVICE, units, streams, states,
-                                       out.ctypes.data, out.nbytes, PTR_HOST, ts_units)
+            rc, mres = mux_raw(cfg, self._mux_es.ptr, int(res.bytes), PTR_DEVICE, units, streams, states,
+                               out.ctypes.data, out.nbytes, PTR_HOST, *rows)
             if rc != OUT_OVERFLOW or attempt:
                 break
-            cap = self._ts_cap = max(int(tres.bytes), 2 * cap)
+            cap = self._mux_caps[fmt] = max(int(mres.bytes), 2 * cap)
         _check(rc)
         for i, k in enumerate(keys):
-            self._ts_states[k] = states[i].copy()
-        return out[:tres.bytes], ts_units, streams
+            kept[k] = states[i].copy()
+        return out[:mres.bytes], mres, rows, units, streams
 
     def mp4_mux_raw(self, cfg, es_ptr, es_bytes, es_kind, units: np.ndarray, streams: np.ndarray, states: np.ndarray,
                     out_ptr, out_cap, out_kind, samples: np.ndarray, frags: np.ndarray) -> tuple:
@@ -859,44 +869,10 @@ class Context:
         holding each stream's run of moof + mdat fragments, MP4_SAMPLE_DTYPE rows (one per drained
         unit), MP4_FRAG_DTYPE rows in output order, and the drain's unit and stream rows.  The mux's
         state rows are kept here by (session, track); tap_disable and session_remove drop them."""
-        if not hasattr(self, "_mp4_states"):
-            self._mp4_states = {}
-        if getattr(self, "_mp4_es", None) is None:
-            self._mp4_es = self.device_alloc(1 << 20)
-        caps = getattr(self, "_tap_caps", [1 << 20, 4096, 64])
-        for attempt in range(2):
-            units = np.zeros(caps[1], dtype=TAP_UNIT_DTYPE)
-            streams = np.zeros(caps[2], dtype=TAP_STREAM_DTYPE)
-            rc, res = self.tap_drain_raw(TAP_FLUSH if flush else 0, self._mp4_es.ptr, self._mp4_es.nbytes, PTR_DEVICE, units, streams)
-            if rc != OUT_OVERFLOW or attempt:
-                break
-            caps = [caps[0], max(caps[1], int(res.units)), max(caps[2], int(res.streams))]
-            self._tap_caps = caps
-            if res.bytes > self._mp4_es.nbytes:
-                self._mp4_es.free()
-                self._mp4_es = None
-                self._mp4_es = self.device_alloc(max(int(res.bytes), 2 * caps[0]))
-        _check(rc)
-        units, streams = units[:res.units], streams[:res.streams]
-        keys = [(int(st["session"]), int(st["track"])) for st in streams]
-        states = np.zeros(len(streams), dtype=MP4_STATE_DTYPE)
-        for i, k in enumerate(keys):
-            if k in self._mp4_states:
-                states[i] = self._mp4_states[k]
-        samples = np.zeros(len(units), dtype=MP4_SAMPLE_DTYPE)
-        frags = np.zeros(max(len(units), 1), dtype=MP4_FRAG_DTYPE)      # a fragment holds at least one unit
-        cap = getattr(self, "_mp4_cap", 1 << 20)
-        for attempt in range(2):
-            out = np.empty(cap, dtype=np.uint8)
-            rc, mres = self.mp4_mux_raw(cfg, self._mp4_es.ptr, int(res.bytes), PTR_DEVICE, units, streams, states,
-                                        out.ctypes.data, out.nbytes, PTR_HOST, samples, frags)
-            if rc != OUT_OVERFLOW or attempt:
-                break
-            cap = self._mp4_cap = max(int(mres.bytes), 2 * cap)
-        _check(rc)
-        for i, k in enumerate(keys):
-            self._mp4_states[k] = states[i].copy()
-        return out[:mres.bytes], samples, frags[:mres.frags], units, streams
+        out, mres, (samples, frags), units, streams = self._drain_and_mux(
+            "mp4", self.mp4_mux_raw, MP4_STATE_DTYPE,       # (a fragment holds at least one unit)
+            lambda n: (np.zeros(n, dtype=MP4_SAMPLE_DTYPE), np.zeros(max(n, 1), dtype=MP4_FRAG_DTYPE)), flush, cfg)
+        return out, samples, frags[:mres.frags], units, streams
 
     def flv_mux_raw(self, cfg, es_ptr, es_bytes, es_kind, units: np.ndarray, streams: np.ndarray, states: np.ndarray,
                     out_ptr, out_cap, out_kind, tags: np.ndarray) -> tuple:
@@ -918,43 +894,9 @@ class Context:
         stream's run of tags, FLV_TAG_DTYPE rows (one per drained unit), and the drain's unit and
         stream rows.  The mux's state rows are kept here by (session, track); tap_disable and
         session_remove drop them."""
-        if not hasattr(self, "_flv_states"):
-            self._flv_states = {}
-        if getattr(self, "_flv_es", None) is None:
-            self._flv_es = self.device_alloc(1 << 20)
-        caps = getattr(self, "_tap_caps", [1 << 20, 4096, 64])
-        for attempt in range(2):
-            units = np.zeros(caps[1], dtype=TAP_UNIT_DTYPE)
-            streams = np.zeros(caps[2], dtype=TAP_STREAM_DTYPE)
-            rc, res = self.tap_drain_raw(TAP_FLUSH if flush else 0, self._flv_es.ptr, self._flv_es.nbytes, PTR_DEVICE, units, streams)
-            if rc != OUT_OVERFLOW or attempt:
-                break
-            caps = [caps[0], max(caps[1], int(res.units)), max(caps[2], int(res.streams))]
-            self._tap_caps = caps
-            if res.bytes > self._flv_es.nbytes:
-                self._flv_es.free()
-                self._flv_es = None
-                self._flv_es = self.device_alloc(max(int(res.bytes), 2 * caps[0]))
-        _check(rc)
-        units, streams = units[:res.units], streams[:res.streams]
-        keys = [(int(st["session"]), int(st["track"])) for st in streams]
-        states = np.zeros(len(streams), dtype=FLV_STATE_DTYPE)
-        for i, k in enumerate(keys):
-            if k in self._flv_states:
-                states[i] = self._flv_states[k]
-        tags = np.zeros(len(units), dtype=FLV_TAG_DTYPE)
-        cap = getattr(self, "_flv_cap", 1 << 20)
-        for attempt in range(2):
-            out = np.empty(cap, dtype=np.uint8)
-            rc, fres = self.flv_mux_raw(cfg, self._flv_es.ptr, int(res.bytes), PTR_DEVICE, units, streams, states,
-                                        out.ctypes.data, out.nbytes, PTR_HOST, tags)
-            if rc != OUT_OVERFLOW or attempt:
-                break
-            cap = self._flv_cap = max(int(fres.bytes), 2 * cap)
-        _check(rc)
-        for i, k in enumerate(keys):
-            self._flv_states[k] = states[i].copy()
-        return out[:fres.bytes], tags, units, streams
+        out, _, (tags,), units, streams = self._drain_and_mux(
+            "flv", self.flv_mux_raw, FLV_STATE_DTYPE, lambda n: (np.zeros(n, dtype=FLV_TAG_DTYPE),), flush, cfg)
+        return out, tags, units, streams
 
     def debug_stall(self, us: int):
         """edgpu_debug_stall: one wave on the context stream waits `us` microseconds of the device
