@@ -183,6 +183,10 @@ int Reflector::RemoveSession(uint32_t session, bool killOutputs) {
     // error), the session lives on and its pushes keep flowing
     if ((err = edgpu_session_remove(fCtx, session, killOutputs ? EDGPU_SESSION_KILL_OUTPUTS : 0))) return err;
     StatsOff(session);                                      // the engine cleared its statistics
+    // ... and its taps: the muxes' rows of its tracks end with it (the next session may get its id)
+    auto ofSession = [&](const auto& k) { return (uint32_t)(k.first >> 32) == session; };
+    fTsStates.erase(std::remove_if(fTsStates.begin(), fTsStates.end(), ofSession), fTsStates.end());
+    fMp4States.erase(std::remove_if(fMp4States.begin(), fMp4States.end(), ofSession), fMp4States.end());
     {
         // later pushes to it are dropped, and what another thread pushed since the flush is
         // discarded (its id may be reused by the next session)

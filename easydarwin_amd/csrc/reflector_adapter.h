@@ -141,7 +141,9 @@ public:
                      std::vector<edgpu_rtp_info>* outInfo);
     int  RemoveOutput(uint32_t handle);
     // the end of a push session (reference count 0, QTSSReflectorModule.cpp:2133-2196):
-    // packets still pending for it are ingested first; killOutputs tears its outputs down with it
+    // packets still pending for it are ingested first; killOutputs tears its outputs down with it.
+    // Once the engine has accepted the removal, the session's statistics, taps and the rows its
+    // tracks' muxes carried (DrainTransportStreams, DrainFragments) are gone with it.
     int  RemoveSession(uint32_t session, bool killOutputs);
     // one pushed packet, exactly as ProcessRTPData hands it to ReflectorStream::PushPacket
     void PushPacket(uint32_t session, uint32_t track, const char* packet, uint32_t packetLen,
@@ -199,13 +201,15 @@ public:
     // The same drain muxed into an MPEG-2 transport stream on the GPU (edgpu_ts_mux): `sink` gets, per
     // stream, its row, one edgpu_ts_unit per drained unit (offsets relative to `packets`) and the
     // 188-byte packets.  The mux's state rows are held here by (session, track) and dropped by
-    // DisableElementaryStream.
+    // DisableElementaryStream and, for every track of the session, by RemoveSession (the engine hands
+    // a removed session's id to the next one); enabling an enabled tap again keeps them.
     typedef std::function<void(const edgpu_tap_stream& stream, const edgpu_ts_unit* units, const uint8_t* packets)> TsSink;
     int  DrainTransportStreams(const TsSink& sink, bool flush = false, const edgpu_ts_config* cfg = nullptr);
     // The same drain muxed into movie fragments on the GPU (edgpu_mp4_mux): `sink` is called once per
     // fragment, in output order, with the fragment's stream row, its row, the sample rows of the whole
     // drain (frag.unit_first indexes them; offsets relative to `bytes`) and the output bytes.  The
-    // mux's state rows are held here by (session, track) and dropped by DisableElementaryStream.
+    // mux's state rows are held here by (session, track) and dropped by DisableElementaryStream and
+    // RemoveSession, as the transport-stream mux's are.
     typedef std::function<void(const edgpu_tap_stream& stream, const edgpu_mp4_frag& frag, const edgpu_mp4_sample* samples,
                                const uint8_t* bytes)> Mp4Sink;
     int  DrainFragments(const Mp4Sink& sink, bool flush = false, const edgpu_mp4_config* cfg = nullptr);

@@ -65,15 +65,16 @@ def test_interleaved_muxes_on_one_context(device):
         assert [len(c.kernel_times(k)) for k in (6, 7, 8)] == [2, 3, 3]
 
 
-def model_drain(fmt, data, units, streams, kept):
+def model_drain(fmt, data, units, streams, kept, cfg=None):
     """What Context.tap_drain_<fmt> owes for a plain drain (data, units, streams): (bytes, a mask of the
-    bytes inside the runs, the model's rows...).  `kept`: the model's states by (session, track); they move on."""
+    bytes inside the runs, the model's rows...).  `kept`: the model's states by (session, track); they move on.
+    cfg: the model's Config (None: the defaults)."""
     keys = [(int(st["session"]), int(st["track"])) for st in streams]
     outs = []
     for fill in (0x00, 0xFF):                               # the bytes between two runs are nobody's
         st = [dict(kept.get(k, MODEL[fmt].new_state())) for k in keys]
         kw = {} if fmt == "ts" else dict(fill=fill)
-        outs.append(MODEL[fmt].mux(None, data.tobytes(), units, streams, st, **kw))
+        outs.append(MODEL[fmt].mux(cfg, data.tobytes(), units, streams, st, **kw))
     kept.update(zip(keys, st))
     a, b = (np.frombuffer(o[0], dtype=np.uint8) for o in outs)
     return (a, a == b) + tuple(outs[0][1:-1])
@@ -123,3 +124,82 @@ def test_drains_of_three_formats_on_one_context():
             if fmt == "mp4":
                 same_rows(got[2], want[3])
             assert np.array_equal(got[-1], streams) and (fmt == "ts" or np.array_equal(got[-2], units))
+
+
+# ---- the growth paths of Context._drain_and_mux: 64 stream rows, 4096 unit rows, a 1-MiB device ES, a 1-MiB output ----
+
+MIB = 1 << 20
+
+
+def one_packet_units(n, seq0, ts0, size, key_every=0):
+    import tap_traces as tt
+    return [tt.header(seq0 + k, ts0 + 3000 * k, True) + tt.nal(5 if key_every and k % key_every == 0 else 1, size, fill=k)
+            for k in range(n)]
+
+
+def same_drain(fmt, got, want, units, streams, what):
+    assert len(got[0]) == len(want[0]) and np.array_equal(got[0][want[1]], want[0][want[1]]), f"{what}: {fmt} bytes"
+    same_rows(got[1], want[2])
+    if fmt == "mp4":
+        same_rows(got[2], want[3])
+    assert np.array_equal(got[-1], streams) and (fmt == "ts" or np.array_equal(got[-2], units)), what
+
+
+def grown_drain(fmt, per_session, crossed):
+    """per_session: [[packet]] -- one tapped session each on two fresh contexts (the caps are the context's:
+    grown ones would hide the retry).  Context.tap_drain_<fmt> of one against the model fed from the plain
+    drain of the other; `crossed(es bytes needed, units, streams, model output bytes)` says that the plain
+    drain's sizes cross the threshold aimed at; then a small drain, which must still match: nothing was
+    consumed twice and the states moved once."""
+    from tap_model import TapModel
+    from test_gpu_tap import add, expect, ingest, same, split
+    with edgpu.Context(**SMALL) as c, edgpu.Context(**SMALL) as plain:
+        ids = [add(c) for _ in per_session]
+        assert [add(plain) for _ in per_session] == ids
+        kept, taps = {}, [TapModel() for _ in ids]
+        more = [one_packet_units(3, 40000, 1 << 30, 30 + k, key_every=2) for k in range(len(ids))]
+        for step, traces in enumerate((per_session, more)):
+            batch = [(s, 0, 1000 * step + j, p) for s, pk in zip(ids, traces) for j, p in enumerate(pk)]
+            for x in (c, plain):
+                ingest(x, batch)
+            data, units, streams = plain.tap_drain()
+            by_key = split(data, units, streams)                # the plain drain grows its buffers too: held to the tap model
+            for s, m, pk in zip(ids, taps, traces):
+                for j, p in enumerate(pk):
+                    m.push(p, 1000 * step + j)
+                same(by_key[(s, 0)], expect(m), f"plain drain {step}, session {s}")
+            want = model_drain(fmt, data, units, streams, kept)
+            need = sum((int(st["bytes"]) + 15) // 16 * 16 for st in streams)
+            print(f"{fmt} drain {step}: es {need} units {len(units)} streams {len(streams)} out {len(want[0])}")
+            assert len(streams) == len(ids) and len(units)
+            assert step or crossed(need, len(units), len(streams), len(want[0]))
+            same_drain(fmt, getattr(c, "tap_drain_" + fmt)(), want, units, streams, f"drain {step}")
+
+
+@pytest.mark.parametrize("fmt", ["ts", "mp4", "flv"])
+def test_binding_drain_of_65_taps(fmt):
+    grown_drain(fmt, [one_packet_units(1 + k % 2, 100 * k, 5000 * k, 9 + k % 23, key_every=1 if k % 3 == 0 else 0) for k in range(65)],
+                lambda es, units, streams, out: streams == 65 > 64 and units <= 4096 and es < MIB and out < MIB)
+
+
+@pytest.mark.parametrize("fmt", ["ts", "mp4", "flv"])
+def test_binding_drain_of_4097_units(fmt):
+    grown_drain(fmt, [one_packet_units(4097, 65000, 7, 20, key_every=1000)],
+                lambda es, units, streams, out: units == 4097 > 4096 and streams == 1 and es < MIB and out < MIB)
+
+
+@pytest.mark.parametrize("fmt", ["ts", "mp4", "flv"])
+def test_binding_drain_over_one_mib_of_es(fmt):
+    """The device ES buffer is freed and a larger one allocated between the two drain attempts."""
+    import tap_traces as tt
+    pk, reached = tt.packetise([[tt.nal(5 if a % 10 == 0 else 1, 28000)] for a in range(40)], mtu=1400, seq0=500)
+    assert "fu-middle" in reached and len(pk) == 840
+    grown_drain(fmt, [pk], lambda es, units, streams, out: es > MIB and units <= 4096 and streams == 1)
+
+
+@pytest.mark.parametrize("fmt", ["ts", "mp4", "flv"])
+def test_binding_output_over_one_mib_from_less_es(fmt):
+    """800 units of 1304 ES bytes: 188 bytes per 184 and the PES headers, 12 bytes per sample and 96 per
+    fragment, or 20 bytes per tag take the output, and nothing else, over 1 MiB."""
+    grown_drain(fmt, [one_packet_units(800, 300, 77, 1300, key_every=200)],
+                lambda es, units, streams, out: es < MIB < out and units <= 4096 and streams == 1)
