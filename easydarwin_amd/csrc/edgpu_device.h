@@ -219,6 +219,62 @@ struct TapPlace {                   // k_tap_place's verdict on a drain
     uint32_t _pad;
 };
 
+// The AAC audio tap (edgpu_aac_tap_*, edgpu_aac.hip), indexed like StreamDev.  As with TapDev a row
+// has one writer at a time: k_aac_scan's wave the drain's outcome (d_*), k_aac_place's lane the
+// placement (p_*) and, when the drain commits, the carried state.  All zero while disabled.
+struct AacDev {                     // 256 B
+    uint32_t enabled, sender;       // the track's RTP sender
+    uint32_t session, track;
+    uint64_t rec;                   // AacRec[cap]: one per queue entry of a drain
+    uint32_t cap;                   // the sender's meta-ring capacity when the buffer was sized
+    uint32_t au_hdr;                // bytes of an AU header: 2 (HBR) or 1 (LBR)
+    uint32_t adts;                  // 1: ADTS framing
+    uint32_t adts23;                // ADTS bytes 2 and 3 without the length bits: byte 2 | byte 3 << 8
+    uint32_t frame_samples, _pad0;
+    // carried between drains
+    uint64_t head;                  // next queue index to examine
+    uint32_t has_prev, prev_seq, pending, _pad1;
+    uint64_t packets, skipped, malformed, orphans, unsupported, missed, frames, discontinuities;
+    // the drain being made
+    uint64_t d_start, d_cut;        // first intact index examined; the head if the drain commits
+    uint64_t d_bytes;
+    uint32_t d_nrec, d_nframes;     // records [0, d_cut - d_start) and frames to deliver
+    uint32_t d_has_prev, d_prev_seq, d_pending, d_disc;
+    uint32_t d_packets, d_skipped, d_malformed, d_orphans, d_unsupported, _pad2;
+    uint64_t p_offset;              // of the stream in `out`
+    uint32_t p_frame_first, _pad3;
+    uint64_t _pad4[4];
+};
+static_assert(sizeof(AacDev) == 256, "AacDev layout");
+
+// What one queue entry contributes to a drain (k_aac_scan -> k_aac_copy).  kAacWhole: `n` AUs from
+// slot byte `src`, their headers from slot byte `hoff`, to `dst`.  kAacPiece: `len` bytes of a chain,
+// `off` bytes into its frame.  kAacLast: a piece that completes the chain whose first fragment is
+// record `first`; the frame goes to `dst`.
+enum : uint8_t { kAacNone = 0, kAacWhole = 1, kAacPiece = 2, kAacLast = 3 };
+struct AacRec {                     // 32 B
+    uint64_t dst;                   // offset in the stream's bytes of the entry's first frame
+    uint32_t frame;                 // index among the stream's frames of the entry's first frame
+    uint32_t first;                 // record of the chain's first fragment
+    uint16_t src;                   // offset in the slot of the first AU byte / the piece
+    uint16_t len;                   // bytes of the piece / of all the entry's AUs
+    uint16_t off;                   // of the piece in its frame
+    uint16_t nfrag;                 // fragments of the completed chain
+    uint16_t hoff;                  // offset in the slot of the first AU header
+    uint16_t size;                  // the completed frame's AU-size
+    uint8_t  kind, n;               // n: AUs emitted
+    uint8_t  flags, _pad;           // EDGPU_AAC_DISCONT on the entry's first frame
+};
+static_assert(sizeof(AacRec) == 32, "AacRec layout");
+
+struct AacPlace {                   // k_aac_place's verdict on a drain
+    uint64_t bytes;
+    uint32_t frames, streams;
+    uint32_t commit;                // everything fits: k_aac_copy runs, the taps' state moved on
+    uint32_t n_items;               // k_aac_copy's work: rounds of records
+    uint64_t _pad;
+};
+
 struct SessionDev {
     uint32_t first_sender;        // senders of track t: first_sender + 2t (+1 for RTCP)
     uint32_t ntracks;

@@ -16,6 +16,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <strings.h>
 #include <vector>
 
 #include <sched.h>
@@ -236,6 +237,7 @@ struct SessionHost {
     std::vector<uint32_t> subs;     // attached subscriber handles
     std::vector<uint32_t> clock_rate;   // per track (rtpmap_clock_rate)
     bool stats = false;             // edgpu_stream_stats_enable
+    std::vector<uint8_t> aac;       // per track: the payload name begins with "MPEG4-GENERIC/" (any case)
 };
 
 // RTCPSRPacket::GetACName (RTCPSRPacket.cpp:87-117): item type 1, length byte, "QTSS<secs>",
@@ -288,9 +290,10 @@ struct edgpu_ctx {
     // (ring 6, a transport-stream mux's kernels: by the first edgpu_ts_mux)
     // (ring 7, a fragmented-MP4 mux's kernels: by the first edgpu_mp4_mux)
     // (ring 8, an FLV mux's kernels: by the first edgpu_flv_mux)
-    hipEvent_t hist[9][kHist][2] = {};
-    uint32_t hist_n[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // pairs recorded (monotonic sequence numbers)
-    uint32_t hist_rd[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // pairs already returned by edgpu_kernel_times
+    // (ring 9, an audio-tap drain's kernels: by the first edgpu_aac_tap_enable)
+    hipEvent_t hist[10][kHist][2] = {};
+    uint32_t hist_n[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // pairs recorded (monotonic sequence numbers)
+    uint32_t hist_rd[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // pairs already returned by edgpu_kernel_times
     // Borrowed end points.  A whole-tick entry (ring 1) ends at its copy kernel's end event
     // (ring 0 sequence number in tick_end[slot]); a keyframe entry (ring 3) starts at the end
     // event of the ingest it indexes (ring 2 sequence number in kf_from[slot]) when nothing ran
@@ -299,7 +302,7 @@ struct edgpu_ctx {
     static const uint32_t kOwnStart = 0xFFFFFFFFu;
     uint32_t tick_end[kHist] = {};
     uint32_t kf_from[kHist] = {};
-    uint32_t last_seq[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // each ring's newest complete pair (edgpu_last_timings)
+    uint32_t last_seq[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // each ring's newest complete pair (edgpu_last_timings)
     bool kf_share = false;                  // the last ingest's end event may start the keyframe entry
     uint64_t fanout_launches = 0;
     int64_t last_now = 0;               // clock of the last edgpu_fanout (backpressure reports)
@@ -341,6 +344,17 @@ struct edgpu_ctx {
     DevVec<edgpu_tap_unit> d_tap_units;
     DevVec<edgpu_tap_stream> d_tap_streams;
     TapPlace* d_tap_place = nullptr;
+    // AAC audio taps (edgpu_aac_tap_*): their own tables, allocated by the first edgpu_aac_tap_enable
+    struct AacHost { void* rec = nullptr; uint64_t cap = 0; uint32_t sender = 0; };
+    DevVec<AacDev> d_aacs;
+    std::map<uint32_t, AacHost> aacs;   // enabled audio taps by stream index: their work buffers
+    std::vector<std::pair<uint32_t, uint64_t>> aac_grown;   // (sender, packets) of tapped rings grown since the last drain
+    bool aac_list_dirty = false;
+    DevVec<uint32_t> d_aac_list, d_aac_items;
+    DevVec<uint8_t> d_aac_out;          // a drain's bytes on their way to host memory
+    DevVec<edgpu_aac_frame> d_aac_frames;
+    DevVec<edgpu_aac_stream> d_aac_streams;
+    AacPlace* d_aac_place = nullptr;
     // The muxes of tapped units (edgpu_ts_mux, edgpu_mp4_mux, edgpu_flv_mux): staging and work
     // buffers only, allocated by the first call and sized from each call's es_bytes and n_units;
     // the state between calls is the caller's.  What every format needs is one set for all of them.
@@ -685,6 +699,10 @@ int edgpu_ctx_destroy(edgpu_ctx* x) {
     x->d_taps.release(); x->d_tap_list.release(); x->d_tap_items.release(); x->d_tap_out.release();
     x->d_tap_units.release(); x->d_tap_streams.release();
     if (x->d_tap_place) (void)hipFree(x->d_tap_place);
+    for (auto& t : x->aacs) (void)hipFree(t.second.rec);
+    x->d_aacs.release(); x->d_aac_list.release(); x->d_aac_items.release(); x->d_aac_out.release();
+    x->d_aac_frames.release(); x->d_aac_streams.release();
+    if (x->d_aac_place) (void)hipFree(x->d_aac_place);
     x->mux.release();
     x->d_ts_ranges.release(); x->d_ts_states.release(); x->d_ts_recs.release(); x->d_ts_base.release(); x->d_ts_rows.release();
     x->d_mp4_ranges.release(); x->d_mp4_states.release(); x->d_mp4_recs.release(); x->d_mp4_frecs.release(); x->d_mp4_srecs.release();
@@ -857,6 +875,7 @@ static int grow_sender(edgpu_ctx* x, uint32_t sender, uint64_t want_pk, uint64_t
     x->ring_bytes += (new_pk - old_pk) * (sizeof(PktMeta) + sizeof(uint32_t)) + (new_by - old_by);
     x->ring_grows++;
     if (new_pk > old_pk && !x->taps.empty()) x->tap_grown.emplace_back(sender, new_pk);   // (its tap's work buffers follow)
+    if (new_pk > old_pk && !x->aacs.empty()) x->aac_grown.emplace_back(sender, new_pk);
     x->index_dirty = true;                      // the work list is sized from the rings
     *grown = true;
     return EDGPU_OK;
@@ -1068,6 +1087,7 @@ int edgpu_session_add(edgpu_ctx* x, const char* sdp, uint32_t sdp_len, int udp_p
     sh.src.resize(sh.ntracks);
     for (auto& h : sh.src) { h.rr_ssrc = (uint32_t)::rand(); h.cname = source_cname(wall_ms / 1000); }
     for (const TrackHost& t : tracks) sh.clock_rate.push_back(rtpmap_clock_rate(t.name));
+    for (const TrackHost& t : tracks) sh.aac.push_back(strncasecmp(t.name.c_str(), "MPEG4-GENERIC/", 14) == 0);
     const uint32_t nsnd = 2 * sh.ntracks;
     if (!reuse) {
         HIP_CHECK(x->d_sessions.reserve(sid + 1, x->stream));
@@ -1176,6 +1196,18 @@ static int tap_clear(edgpu_ctx* x, uint32_t row) {
     return EDGPU_OK;
 }
 
+// The same for the audio tap of stream row `row`.
+static int aac_clear(edgpu_ctx* x, uint32_t row) {
+    auto it = x->aacs.find(row);
+    if (it == x->aacs.end()) return EDGPU_OK;
+    HIP_CHECK(hipMemsetAsync(x->d_aacs.ptr + row, 0, sizeof(AacDev), x->stream));
+    HIP_CHECK(wsync(x, x->stream));
+    (void)hipFree(it->second.rec);
+    x->aacs.erase(it);
+    x->aac_list_dirty = true;
+    return EDGPU_OK;
+}
+
 // Deactivates subscriber `handle`'s sub-streams (host mirror + device flag, enqueued; the caller
 // synchronises) and returns its SubDev range to the free list.
 static int detach_subscriber(edgpu_ctx* x, uint32_t handle) {
@@ -1224,6 +1256,7 @@ int edgpu_session_remove(edgpu_ctx* x, uint32_t session, uint32_t flags) {
     // from here the session ends: its statistics with it (a removal refused above leaves them on)
     if (sh.stats) { int r = stats_clear(x, sh); if (r) return r; }
     for (uint32_t t = 0; t < sh.ntracks; t++) { int r = tap_clear(x, sh.first_stream + t); if (r) return r; }
+    for (uint32_t t = 0; t < sh.ntracks; t++) { int r = aac_clear(x, sh.first_stream + t); if (r) return r; }
     for (uint32_t i = 0; i < nsnd; i++) {
         const uint32_t gs = sh.first_sender + i;
         x->work_cap_needed -= ((uint64_t)old[i].pk_mask + 1) / 16 + 1;
@@ -2600,6 +2633,140 @@ int edgpu_tap_drain(edgpu_ctx* x, uint32_t flags, void* out, uint64_t out_cap, i
     return EDGPU_OK;
 }
 
+// ---- AAC audio taps (edgpu_aac_tap_*; edgpu_aac.hip): the H.264 tap's paths over their own tables ----
+static int aac_buffers(edgpu_ctx::AacHost& h, uint64_t cap) {
+    void* rec = nullptr;
+    if (dmalloc(&rec, cap * sizeof(AacRec)) != hipSuccess) { (void)hipGetLastError(); return fail(EDGPU_OUT_OF_MEMORY, "audio tap records"); }
+    if (h.rec) (void)hipFree(h.rec);
+    h.rec = rec; h.cap = cap;
+    return EDGPU_OK;
+}
+
+static bool aac_config_ok(const edgpu_aac_config* c) {
+    return c && (c->mode == EDGPU_AAC_HBR || c->mode == EDGPU_AAC_LBR) && c->framing <= EDGPU_AAC_RAW &&
+           c->object_type >= 1 && c->object_type <= 4 && c->freq_index <= 12 && c->channels >= 1 && c->channels <= 7;
+}
+
+int edgpu_aac_tap_enable(edgpu_ctx* x, uint32_t session, uint32_t track, const edgpu_aac_config* cfg) {
+    if (!x || !live_session(x, session) || track >= x->sessions[session].ntracks) return fail(EDGPU_BAD_ARGUMENT, "bad session or track");
+    if (!aac_config_ok(cfg)) return fail(EDGPU_BAD_ARGUMENT, "bad audio tap config");
+    const SessionHost& sh = x->sessions[session];
+    if (track >= sh.aac.size() || !sh.aac[track])
+        return fail(EDGPU_BAD_ARGUMENT, "the audio tap depacketises RFC 3640 only: the track's payload name does not begin with \"MPEG4-GENERIC/\"");
+    DEVICE_ENTER(x);
+    const uint32_t row = sh.first_stream + track, sender = sh.first_sender + 2 * track;
+    SenderDev D;
+    {
+        Readback rb(x);
+        HIP_CHECK(rb.add(&D, x->d_senders.ptr + sender, sizeof(D)));
+        HIP_CHECK(rb.run());
+    }
+    const size_t old_cap = x->d_aacs.cap;
+    HIP_CHECK(x->d_aacs.reserve(x->nstreams, x->stream));
+    if (x->d_aacs.cap > old_cap)
+        HIP_CHECK(hipMemsetAsync(x->d_aacs.ptr + old_cap, 0, (x->d_aacs.cap - old_cap) * sizeof(AacDev), x->stream));
+    if (!x->d_aac_place && dmalloc(&x->d_aac_place, sizeof(AacPlace)) != hipSuccess) return fail(EDGPU_OUT_OF_MEMORY, "audio tap placement");
+    if (!x->hist[9][0][0])
+        for (auto& s : x->hist[9]) for (auto& e : s) HIP_CHECK(hipEventCreate(&e));
+    edgpu_ctx::AacHost& h = x->aacs[row];
+    const uint64_t cap = (uint64_t)D.pk_mask + 1;
+    if (h.cap != cap) {
+        if (int r = aac_buffers(h, cap)) { if (!h.rec) x->aacs.erase(row); return r; }
+    }
+    h.sender = sender;
+    AacDev T;
+    memset(&T, 0, sizeof(T));
+    T.enabled = 1; T.sender = sender; T.session = session; T.track = track;
+    T.rec = (uint64_t)(uintptr_t)h.rec; T.cap = (uint32_t)cap;
+    T.au_hdr = cfg->mode == EDGPU_AAC_HBR ? 2 : 1;
+    T.adts = cfg->framing == EDGPU_AAC_RAW ? 0 : 1;
+    T.adts23 = (((cfg->object_type - 1) << 6) | (cfg->freq_index << 2) | (cfg->channels >> 2)) | (((cfg->channels & 3) << 6) << 8);
+    T.frame_samples = cfg->frame_samples ? cfg->frame_samples : 1024;
+    T.head = D.head;                            // the tap starts at the next packet enqueued
+    HIP_CHECK(hipMemcpyAsync(x->d_aacs.ptr + row, &T, sizeof(T), hipMemcpyHostToDevice, x->stream));
+    HIP_CHECK(wsync(x, x->stream));             // `T` is on the stack
+    x->aac_list_dirty = true;
+    return EDGPU_OK;
+}
+
+int edgpu_aac_tap_disable(edgpu_ctx* x, uint32_t session, uint32_t track) {
+    if (!x || !live_session(x, session) || track >= x->sessions[session].ntracks) return fail(EDGPU_BAD_ARGUMENT, "bad session or track");
+    DEVICE_ENTER(x);
+    return aac_clear(x, x->sessions[session].first_stream + track);
+}
+
+int edgpu_aac_tap_drain(edgpu_ctx* x, uint32_t flags, void* out, uint64_t out_cap, int ptr_kind, edgpu_aac_frame* frames,
+                        uint32_t frame_cap, edgpu_aac_stream* streams, uint32_t stream_cap, edgpu_aac_result* result) {
+    if (!x || !result || (flags & ~EDGPU_AAC_FLUSH) || (!out && out_cap) || (!frames && frame_cap) || (!streams && stream_cap))
+        return fail(EDGPU_BAD_ARGUMENT, "bad argument");
+    if (ptr_kind != EDGPU_PTR_HOST && ptr_kind != EDGPU_PTR_DEVICE && ptr_kind != EDGPU_PTR_PINNED)
+        return fail(EDGPU_BAD_ARGUMENT, "bad ptr_kind");
+    const bool device_out = ptr_kind == EDGPU_PTR_DEVICE;
+    if (device_out && ((uintptr_t)out & 15)) return fail(EDGPU_BAD_ARGUMENT, "a device `out` must be 16-B aligned");
+    memset(result, 0, sizeof(*result));
+    if (x->aacs.empty()) return EDGPU_OK;       // nothing launched, allocated, recorded or copied
+    DEVICE_ENTER(x);
+    const uint32_t ntaps = (uint32_t)x->aacs.size();
+    // tapped rings that grew: work buffers of the new capacity (no drain is in flight: every drain syncs)
+    for (const auto& g : x->aac_grown)
+        for (auto& t : x->aacs)
+            if (t.second.sender == g.first && t.second.cap < g.second) {
+                if (int r = aac_buffers(t.second, g.second)) return r;
+                const uint64_t rec = (uint64_t)(uintptr_t)t.second.rec;
+                const uint32_t cap = (uint32_t)g.second;
+                HIP_CHECK(hipMemcpyAsync(&x->d_aacs.ptr[t.first].rec, &rec, sizeof(rec), hipMemcpyHostToDevice, x->stream));
+                HIP_CHECK(hipMemcpyAsync(&x->d_aacs.ptr[t.first].cap, &cap, sizeof(cap), hipMemcpyHostToDevice, x->stream));
+                HIP_CHECK(wsync(x, x->stream));
+            }
+    x->aac_grown.clear();
+    if (x->aac_list_dirty) {
+        std::vector<uint32_t> list;
+        for (const auto& t : x->aacs) list.push_back(t.first);     // ascending rows: (session, track) order
+        HIP_CHECK(x->d_aac_list.reserve(ntaps, x->stream));
+        HIP_CHECK(x->d_aac_items.reserve((size_t)ntaps + 1, x->stream));
+        HIP_CHECK(x->d_aac_streams.reserve(ntaps, x->stream));
+        HIP_CHECK(hipMemcpyAsync(x->d_aac_list.ptr, list.data(), ntaps * sizeof(uint32_t), hipMemcpyHostToDevice, x->stream));
+        HIP_CHECK(wsync(x, x->stream));         // `list` is on the stack
+        x->aac_list_dirty = false;
+    }
+    AacPlace pl;
+    for (int attempt = 0;; attempt++) {
+        AacParams p;
+        p.senders = x->d_senders.ptr; p.taps = x->d_aacs.ptr; p.list = x->d_aac_list.ptr;
+        p.ntaps = ntaps; p.nsenders = x->nsenders; p.flags = flags;
+        p.frame_cap = (uint32_t)std::min<uint64_t>(frame_cap, x->d_aac_frames.cap);
+        p.stream_cap = stream_cap;
+        p.out_cap = device_out ? out_cap : std::min<uint64_t>(out_cap, x->d_aac_out.cap);
+        p.out = device_out ? (uint8_t*)out : x->d_aac_out.ptr;
+        p.frames = x->d_aac_frames.ptr; p.streams = x->d_aac_streams.ptr;
+        p.items = x->d_aac_items.ptr; p.place = x->d_aac_place;
+        HIP_CHECK(hist_mark(x, 9, 0));
+        HIP_CHECK(launch_aac_drain(p, (uint32_t)std::max(x->num_cus * 4, 1), x->stream));
+        HIP_CHECK(hist_mark(x, 9, 1));
+        {
+            Readback rb(x);
+            HIP_CHECK(rb.add(&pl, x->d_aac_place, sizeof(pl)));
+            HIP_CHECK(rb.run());
+        }
+        if (pl.commit) break;
+        result->bytes = pl.bytes; result->frames = pl.frames; result->streams = pl.streams;
+        const bool fits = pl.bytes <= out_cap && pl.frames <= frame_cap && pl.streams <= stream_cap;
+        if (!fits || attempt)
+            return fail(EDGPU_OUT_OVERFLOW, "audio tap drain: " + std::to_string(pl.bytes) + " bytes, " + std::to_string(pl.frames) +
+                                            " frames, " + std::to_string(pl.streams) + " streams needed; nothing was consumed");
+        // the caller has room, the context's staging did not: grown, and the drain made again
+        if (!device_out) HIP_CHECK(x->d_aac_out.reserve(pl.bytes, x->stream));
+        HIP_CHECK(x->d_aac_frames.reserve(pl.frames, x->stream));
+    }
+    result->bytes = pl.bytes; result->frames = pl.frames; result->streams = pl.streams;
+    Readback rb(x);
+    if (!device_out) HIP_CHECK(rb.add(out, x->d_aac_out.ptr, pl.bytes));
+    HIP_CHECK(rb.add(frames, x->d_aac_frames.ptr, (size_t)pl.frames * sizeof(edgpu_aac_frame)));
+    HIP_CHECK(rb.add(streams, x->d_aac_streams.ptr, (size_t)pl.streams * sizeof(edgpu_aac_stream)));
+    HIP_CHECK(rb.run());
+    return EDGPU_OK;
+}
+
 // ---- MPEG-2 transport-stream mux of tapped access units (edgpu_ts_mux; edgpu_ts.hip) ----
 static uint32_t crc32_mpeg2(const uint8_t* p, size_t n) {
     uint32_t crc = 0xFFFFFFFFu;
@@ -2959,7 +3126,7 @@ int edgpu_flv_mux(edgpu_ctx* x, const edgpu_flv_config* cfg, const void* es, uin
 }
 
 int edgpu_kernel_times(edgpu_ctx* x, int which, float* out_ms, uint32_t max_n, uint32_t* out_n) {
-    if (!x || which < 0 || which > 8 || (!out_ms && max_n)) return fail(EDGPU_BAD_ARGUMENT, "bad argument");
+    if (!x || which < 0 || which > 9 || (!out_ms && max_n)) return fail(EDGPU_BAD_ARGUMENT, "bad argument");
     DEVICE_ENTER(x);
     HIP_CHECK(sync_all(x));
     const uint32_t n = std::min<uint32_t>(x->hist_n[which] - x->hist_rd[which], edgpu_ctx::kHist);

@@ -224,6 +224,26 @@ struct TapParams {
 };
 hipError_t launch_tap_drain(const TapParams& p, uint32_t copy_blocks, hipStream_t st);
 
+// The AAC audio tap (edgpu_aac.hip): one drain is k_aac_scan (a wave per enabled tap), k_aac_place
+// (one workgroup) and k_aac_copy.
+constexpr uint32_t kAacRound = 64;                  // queue entries per scan round and per copy item
+struct AacParams {
+    const SenderDev* senders;
+    AacDev* taps;
+    const uint32_t* list;       // the enabled taps' rows, ascending
+    uint32_t ntaps;
+    uint32_t nsenders;
+    uint32_t flags;             // EDGPU_AAC_FLUSH
+    uint32_t frame_cap, stream_cap;
+    uint64_t out_cap;
+    uint8_t* out;
+    edgpu_aac_frame* frames;    // device staging of the caller's arrays
+    edgpu_aac_stream* streams;
+    uint32_t* items;            // ntaps + 1: exclusive sums of the taps' record rounds
+    AacPlace* place;
+};
+hipError_t launch_aac_drain(const AacParams& p, uint32_t copy_blocks, hipStream_t st);
+
 // The transport-stream mux (edgpu_ts_mux, edgpu_ts.hip): k_ts_plan (a wave per stream row),
 // k_ts_place (one workgroup) and k_ts_pack (flat over the output's 16-B words).
 struct TsRec {                  // what k_ts_plan leaves per unit for k_ts_pack; zero for a unit no row covers

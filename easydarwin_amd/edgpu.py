@@ -48,6 +48,7 @@ EXPORTED = [
     "edgpu_stream_stats_get", "edgpu_session_bitrate",
     "edgpu_tap_enable", "edgpu_tap_disable", "edgpu_tap_drain", "edgpu_ts_mux",
     "edgpu_flv_mux", "edgpu_flv_header",
+    "edgpu_aac_config_parse", "edgpu_aac_tap_enable", "edgpu_aac_tap_disable", "edgpu_aac_tap_drain",
 ]
 # the fragmented-MP4 entry points, listed apart: tests/test_abi.py compares EXPORTED with the names its
 # pattern finds in the header, and that pattern stops at a digit (tests/test_mp4_abi.py checks these)
@@ -276,6 +277,39 @@ class FlvResult(C.Structure):
 
 FLV_FILE, FLV_META, FLV_SEQ = 1, 2, 4
 
+
+class AacConfig(C.Structure):
+    """edgpu_aac_config: what the audio tap needs to know of an MPEG4-GENERIC track."""
+    _fields_ = [("mode", C.c_uint32), ("framing", C.c_uint32), ("object_type", C.c_uint32), ("freq_index", C.c_uint32),
+                ("channels", C.c_uint32), ("frame_samples", C.c_uint32)]
+
+
+class AacFrame(C.Structure):
+    """edgpu_aac_frame: one AAC frame of an audio-tap drain."""
+    _fields_ = [("offset", C.c_uint64), ("bytes", C.c_uint32), ("rtp_ts", C.c_uint32), ("arrival_ms", C.c_int64),
+                ("flags", C.c_uint32), ("first_seq", C.c_uint32), ("n_packets", C.c_uint32), ("au_index", C.c_uint32),
+                ("stream", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class AacStream(C.Structure):
+    """edgpu_aac_stream: one enabled audio tap's part of a drain and its cumulative counters."""
+    _fields_ = [("session", C.c_uint32), ("track", C.c_uint32), ("offset", C.c_uint64), ("bytes", C.c_uint64),
+                ("frame_first", C.c_uint32), ("frame_count", C.c_uint32),
+                ("packets", C.c_uint64), ("skipped", C.c_uint64), ("malformed", C.c_uint64), ("orphans", C.c_uint64),
+                ("unsupported", C.c_uint64), ("missed", C.c_uint64), ("frames", C.c_uint64), ("discontinuities", C.c_uint64)]
+
+
+class AacResult(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("frames", C.c_uint32), ("streams", C.c_uint32)]
+
+
+AAC_HBR, AAC_LBR = 1, 2
+AAC_ADTS, AAC_RAW = 1, 2
+AAC_MAX_AUS = 16
+AAC_DISCONT, AAC_FRAGMENTED = 1, 2
+AAC_FLUSH = 1
+AAC_ROUND = 64              # queue entries per round of the audio tap's scan kernel
+
 TS_AUD, TS_NOAUD = 1, 2
 TS_PACKET = 188
 
@@ -302,6 +336,10 @@ FLV_STATE_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in FlvState._fields_])
 FLV_TAG_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in FlvTag._fields_])
 assert FLV_STATE_DTYPE.itemsize == C.sizeof(FlvState) == 24 and FLV_TAG_DTYPE.itemsize == C.sizeof(FlvTag) == 40
 assert C.sizeof(FlvConfig) == 16 and C.sizeof(FlvResult) == 16
+AAC_FRAME_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in AacFrame._fields_])
+AAC_STREAM_DTYPE = np.dtype([(name, _NP_OF[t]) for name, t in AacStream._fields_])
+assert AAC_FRAME_DTYPE.itemsize == C.sizeof(AacFrame) == 48 and AAC_STREAM_DTYPE.itemsize == C.sizeof(AacStream) == 96
+assert C.sizeof(AacConfig) == 24 and C.sizeof(AacResult) == 16
 PKT_DTYPE = np.dtype([("slot", "<u4"), ("len", "<u2"), ("channel", "u1"), ("flags", "u1"),
                       ("arrival_ms", "<i8")])
 OUT_DTYPE = np.dtype([("offset", "<u8"), ("len", "<u4"), ("packet_id", "<u4")])
@@ -425,6 +463,10 @@ def load(path: str = LIB_PATH):
         "edgpu_tap_enable": (I32, [P, U32, U32]),
         "edgpu_tap_disable": (I32, [P, U32, U32]),
         "edgpu_tap_drain": (I32, [P, U32, P, U64, I32, P, U32, P, U32, C.POINTER(TapResult)]),
+        "edgpu_aac_config_parse": (I32, [C.c_char_p, U32, U32, C.POINTER(AacConfig)]),
+        "edgpu_aac_tap_enable": (I32, [P, U32, U32, C.POINTER(AacConfig)]),
+        "edgpu_aac_tap_disable": (I32, [P, U32, U32]),
+        "edgpu_aac_tap_drain": (I32, [P, U32, P, U64, I32, P, U32, P, U32, C.POINTER(AacResult)]),
         "edgpu_ts_mux": (I32, [P, C.POINTER(TsConfig), P, U64, I32, P, U32, P, U32, P, P, U64, I32, P, C.POINTER(TsResult)]),
         "edgpu_mp4_mux": (I32, [P, C.POINTER(Mp4Config), P, U64, I32, P, U32, P, U32, P, P, U64, I32, P, P, U32,
                                 C.POINTER(Mp4Result)]),
@@ -484,6 +526,19 @@ def mp4_init(sps: bytes, pps: bytes, timescale: int = 0) -> bytes:
     return buf.raw[:n.value]
 
 
+def aac_config_parse(sdp, track: int, framing: int = 0, frame_samples: int = 0) -> AacConfig:
+    """The audio tap's config of the SDP's `track`-th media section, from its a=fmtp line
+    (edgpu_aac_config_parse); `framing` (AAC_ADTS / AAC_RAW) and `frame_samples` are set as given.
+    Host only."""
+    sdp = sdp.encode() if isinstance(sdp, str) else bytes(sdp)
+    cfg = AacConfig()
+    rc = load().edgpu_aac_config_parse(sdp, len(sdp), track, C.byref(cfg))
+    if rc != 0:
+        raise EdgpuError(rc, "edgpu_aac_config_parse: no fmtp line the audio tap supports in media section %d" % track)
+    cfg.framing, cfg.frame_samples = framing, frame_samples
+    return cfg
+
+
 def flv_header(sps: bytes, pps: bytes, timestamp_ms: int = 0, parts: int = 0) -> bytes:
     """What stands before the tags of an FLV stream (edgpu_flv_header): the file header, onMetaData and
     the AVC sequence header at `timestamp_ms`, or those of them `parts` names (FLV_FILE | FLV_META |
@@ -520,6 +575,7 @@ class Context:
         self._mux_es = None
         self._mux_states = {"ts": {}, "mp4": {}, "flv": {}}
         self._mux_caps = {}
+        self.aac_taps = {}          # (session, track) -> AacConfig of the enabled audio taps
 
     def close(self):
         if self.h:
@@ -556,6 +612,8 @@ class Context:
         for kept in self._mux_states.values():
             for k in [k for k in kept if k[0] == session]:
                 del kept[k]
+        for k in [k for k in self.aac_taps if k[0] == session]:
+            del self.aac_taps[k]
 
     def subscriber_add(self, session: int, transport: int = TRANSPORT_UDP) -> int:
         out = C.c_uint32()
@@ -781,6 +839,47 @@ class Context:
         _check(rc)
         data = buf[:res.bytes] if buf is not None else int(res.bytes)
         return data, units[:res.units], streams[:res.streams]
+
+    def aac_tap_enable(self, session: int, track: int, cfg: AacConfig):
+        """Enables (or resets) the AAC audio tap of an MPEG4-GENERIC track, from the next packet
+        enqueued (edgpu_aac_tap_enable).  `cfg`: aac_config_parse of the SDP, its framing set as wanted."""
+        _check(self.lib.edgpu_aac_tap_enable(self.h, session, track, C.byref(cfg)))
+        self.aac_taps[(session, track)] = cfg
+
+    def aac_tap_disable(self, session: int, track: int):
+        _check(self.lib.edgpu_aac_tap_disable(self.h, session, track))
+        self.aac_taps.pop((session, track), None)
+
+    def aac_tap_drain_raw(self, flags, out_ptr, out_cap, ptr_kind, frames: np.ndarray, streams: np.ndarray) -> tuple:
+        """edgpu_aac_tap_drain as it is: (status, AacResult)."""
+        res = AacResult()
+        rc = self.lib.edgpu_aac_tap_drain(self.h, flags, C.c_void_p(out_ptr), out_cap, ptr_kind,
+                                          _ptr(frames) if len(frames) else None, len(frames),
+                                          _ptr(streams) if len(streams) else None, len(streams), C.byref(res))
+        return rc, res
+
+    def aac_tap_drain(self, flush: bool = False, out=None):
+        """Drains every enabled audio tap (edgpu_aac_tap_drain): (bytes, frames, streams) -- a uint8
+        array (or the byte count when `out` is a DeviceBuffer the kernel wrote), AAC_FRAME_DTYPE rows
+        and AAC_STREAM_DTYPE rows.  Grows its buffers and retries once on overflow (nothing is
+        consumed by a call that overflows); a device `out` is not grown."""
+        caps = getattr(self, "_aac_caps", [1 << 18, 4096, 64])
+        for attempt in range(2):
+            frames = np.zeros(caps[1], dtype=AAC_FRAME_DTYPE)
+            streams = np.zeros(caps[2], dtype=AAC_STREAM_DTYPE)
+            if out is None:
+                buf = np.empty(caps[0], dtype=np.uint8)
+                rc, res = self.aac_tap_drain_raw(AAC_FLUSH if flush else 0, buf.ctypes.data, buf.nbytes, PTR_HOST, frames, streams)
+            else:
+                buf = None
+                rc, res = self.aac_tap_drain_raw(AAC_FLUSH if flush else 0, out.ptr, out.nbytes, PTR_DEVICE, frames, streams)
+            if rc != OUT_OVERFLOW or attempt:
+                break
+            caps = [max(caps[0], int(res.bytes)), max(caps[1], int(res.frames)), max(caps[2], int(res.streams))]
+            self._aac_caps = caps
+        _check(rc)
+        data = buf[:res.bytes] if buf is not None else int(res.bytes)
+        return data, frames[:res.frames], streams[:res.streams]
 
     def ts_mux_raw(self, cfg, es_ptr, es_bytes, es_kind, units: np.ndarray, streams: np.ndarray, states: np.ndarray,
                    out_ptr, out_cap, out_kind, ts_units: np.ndarray) -> tuple:

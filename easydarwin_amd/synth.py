@@ -41,8 +41,17 @@ def make_sdp(tracks: list[TrackSpec], name: str = "EasyPusher") -> str:
     for i, tr in enumerate(tracks):
         lines.append(f"m={tr.media} 0 RTP/AVP {tr.pt}")
         lines.append(f"a=rtpmap:{tr.pt} {tr.payload}")
+        if tr.extra.get("rfc3640"):             # opt-in: the fmtp line of the packets _audio then emits
+            lines.append(f"a=fmtp:{tr.pt} {AAC_HBR_FMTP}")
         lines.append(f"a=control:trackID={i + 1}")
     return "\r\n".join(lines) + "\r\n"
+
+
+# extra={"rfc3640": True} on an MPEG4-GENERIC track: its packets carry an RFC 3640 AAC-hbr AU-header
+# section (one AU per packet, the packet sizes unchanged) and its SDP section this fmtp line.  Off by
+# default: the goldens depend on the default bytes.
+AAC_HBR_FMTP = ("streamtype=5; profile-level-id=15; mode=AAC-hbr; config=1190; "
+                "sizelength=13; indexlength=3; indexdeltalength=3")
 
 
 def rtp_header(seq: int, ts: int, ssrc: int, pt: int, marker: bool, cc: int = 0) -> bytes:
@@ -161,6 +170,10 @@ def _audio(rng, tr: TrackSpec, duration_ms: int, t0: int):
             sz = int(rng.integers(200, 401))
         else:
             sz = size
+        if size is None and tr.extra.get("rfc3640"):
+            body = max(sz - 4, 1)
+            out.append((t, r.packet(i * spp, True, struct.pack(">HH", 16, body << 3) + r.rand(body))))
+            continue
         out.append((t, r.packet(i * spp, True, r.rand(sz))))
     return r, out
 

@@ -875,7 +875,8 @@ int  edgpu_session_bitrate(edgpu_ctx* ctx, uint32_t session, uint32_t* bps);
  * Between drains a tap carries its head, the previous good packet's sequence number, a
  * pending-damage bit and the counters.  Taps belong to the owning context: they do not travel in
  * session images, a replica session starts without them, edgpu_session_remove clears them.
- * Out of scope: audio, packetization-mode 2, H.265, reordering.  (The drained units as an MPEG-2
+ * Out of scope: packetization-mode 2, H.265, reordering.  Audio has a tap of its own: the section
+ * "AAC audio tap" below, edgpu_aac_tap_enable and its drain.  (The drained units as an MPEG-2
  * transport stream: edgpu_ts_mux below; as fragmented MP4: edgpu_mp4_mux; as FLV tags: edgpu_flv_mux.) */
 #define EDGPU_TAP_KEY       1u
 #define EDGPU_TAP_PARAMS    2u
@@ -1216,12 +1217,141 @@ int  edgpu_flv_mux(edgpu_ctx* ctx, const edgpu_flv_config* cfg /* NULL: defaults
 int  edgpu_flv_header(const uint8_t* sps, uint32_t sps_len, const uint8_t* pps, uint32_t pps_len, uint32_t timestamp_ms,
                       uint32_t parts, uint8_t* out, uint64_t cap, uint64_t* out_len);
 
+/* ---- AAC audio tap ----
+ *
+ * An opt-in tap per MPEG4-GENERIC track turns the track's RTP sender ring into AAC frames on the
+ * GPU (RFC 3640, AAC-hbr and AAC-lbr, not interleaved), each behind a generated ADTS header or raw,
+ * with an index of the frames -- the audio half of what a recorder or a muxer needs.  It has its own
+ * entry points, tables and kernels (edgpu_aac.hip): an RFC 3640 packet carries many units where the
+ * H.264 tap builds one unit from many packets, and edgpu_tap_enable refuses every other payload by
+ * contract.  With no audio tap enabled nothing is launched, allocated, recorded or copied; a tap
+ * reads the rings and never pins a packet.  tests/aac_model.py is the executable statement of the
+ * rules below.
+ *
+ * A drain takes the queue entries of the track's RTP sender in queue order from the tap's head,
+ * each with its final length; empty entries are ignored.  Entries that left the ring before a drain
+ * examined them count in `missed`.
+ *   Parse.  Word for word the H.264 tap's: version, CC, X, P, empty payload.  Bad packets count in
+ *     `skipped` and are otherwise absent (a gap follows naturally if they had a sequence number).
+ *   Gap.  A good packet has a gap when a previous good packet exists and its sequence number is
+ *     not that packet's + 1 (mod 2^16).  Nothing is reordered.
+ *   AU-header section.  For a payload of P bytes and an AU header of h bytes (2 for HBR, 1 for
+ *     LBR): P < 2, a BE16 bit count of 0, or one that is not a multiple of 8h: the whole packet is
+ *     dropped (`malformed`).  n is that count / 8h and H = 2 + n h; H > P: dropped (`malformed`).
+ *     n > EDGPU_AAC_MAX_AUS: dropped (`unsupported`).  A non-zero AU-index in the first header or
+ *     AU-index-delta in a later one (the header's low 3 bits in HBR, low 2 in LBR) means
+ *     interleaving: dropped (`unsupported`).  AU-size is the header's top 13 bits (HBR) or top 6
+ *     bits (LBR).  The checks are made in this order.
+ *   Whole frames.  If n > 1, or n == 1 with size0 <= P - H, the AUs are emitted in order from
+ *     payload byte H.  An AU of size 0, or one that ends past the payload, ends the packet there:
+ *     the packet counts once in `malformed`, the AUs before it stay.  Bytes after the last AU are
+ *     ignored.
+ *   Fragments (HBR only).  A packet with n == 1 and size0 > P - H is a fragment: it carries P - H
+ *     bytes of a frame of size0 bytes.  In LBR it is dropped (`malformed`); under ADTS framing with
+ *     size0 > 8184 it is dropped (`unsupported`: the ADTS length field has 13 bits).  A fragment
+ *     continues the open chain iff a chain is open, the packet has no gap, and its timestamp and
+ *     size0 equal the chain's; otherwise it opens a new chain.  A continuing fragment that would
+ *     overrun size0 is dropped (`malformed`) and the chain is abandoned.  The chain completes when
+ *     its bytes equal size0: the frame is emitted, whatever the marker bit says, and the chain is
+ *     closed.  Every other good packet, dropped or not, abandons an open chain.  The fragments of an
+ *     abandoned chain count in `orphans`, at the packet that abandons it.
+ *   Whole units only.  A drain consumes every entry before the first fragment of a chain still
+ *     open at the end of the queue; that fragment and everything behind it waits, and their counters
+ *     wait with them -- except that a chain this fragment abandoned is consumed: its fragments count
+ *     in `orphans` now and the discontinuity stays pending.  EDGPU_AAC_FLUSH consumes everything; the
+ *     open chain's fragments then count in `orphans`.
+ *   Frame rows.  rtp_ts is the packet's timestamp + k x frame_samples (mod 2^32) for the k-th AU
+ *     of the packet (au_index k); arrival_ms and first_seq are the packet's, a chain's first
+ *     fragment's; n_packets is 1, or the chain's fragments.  EDGPU_AAC_FRAGMENTED: rebuilt from a
+ *     chain.  EDGPU_AAC_DISCONT: the first frame emitted after a gap, a dropped packet, an abandoned
+ *     chain or missed entries -- a muxer must not assume it follows the previous frame.
+ *   ADTS.  Under EDGPU_AAC_ADTS seven bytes precede each frame, with L = size + 7, prof =
+ *     object_type - 1, f = freq_index, c = channels: FF, F1, (prof<<6)|(f<<2)|(c>>2),
+ *     ((c&3)<<6)|(L>>11), (L>>3)&FF, ((L&7)<<5)|1F, FC.  (AAC-LC 44.1 kHz stereo: FF F1 50 80.)
+ *   Layout.  A stream's frames follow each other without a gap from a 16-B aligned stream offset,
+ *     so a stream's run under ADTS framing is an .aac file as it stands.
+ * Between drains a tap carries its head, the previous good packet's sequence number, a
+ * pending-discontinuity bit and the counters; it carries no chain, since open chains are never
+ * consumed.  Taps belong to the owning context: they do not travel in session images, a replica
+ * session starts without them, edgpu_session_remove clears them.
+ * Out of scope: audio in edgpu_ts_mux / edgpu_mp4_mux / edgpu_flv_mux, other audio payloads, LATM,
+ * interleaved RFC 3640, CTS / DTS / auxiliary sections, reordering, taps on replica sessions, module
+ * prefs, a method of the C++ adapter. */
+#define EDGPU_AAC_HBR        1u     /* edgpu_aac_config.mode: sizelength 13, indexlength 3, indexdeltalength 3 */
+#define EDGPU_AAC_LBR        2u     /* sizelength 6, indexlength 2, indexdeltalength 2 */
+#define EDGPU_AAC_ADTS       1u     /* edgpu_aac_config.framing (0 means ADTS) */
+#define EDGPU_AAC_RAW        2u
+#define EDGPU_AAC_MAX_AUS   16u     /* AU headers per packet */
+#define EDGPU_AAC_DISCONT    1u     /* edgpu_aac_frame.flags */
+#define EDGPU_AAC_FRAGMENTED 2u
+#define EDGPU_AAC_FLUSH      1u     /* edgpu_aac_tap_drain flags */
+typedef struct edgpu_aac_config {
+    uint32_t mode;              /* EDGPU_AAC_HBR / EDGPU_AAC_LBR */
+    uint32_t framing;           /* 0 or EDGPU_AAC_ADTS, EDGPU_AAC_RAW */
+    uint32_t object_type;       /* 1..4   \                                               */
+    uint32_t freq_index;        /* 0..12   > the first 13 bits of the AudioSpecificConfig */
+    uint32_t channels;          /* 1..7   /                                               */
+    uint32_t frame_samples;     /* RTP ticks per frame; 0 means 1024 */
+} edgpu_aac_config;
+typedef struct edgpu_aac_frame {    /* one AAC frame */
+    uint64_t offset;            /* of its first byte (its ADTS header's under ADTS framing) in `out` */
+    uint32_t bytes;             /* the ADTS header included */
+    uint32_t rtp_ts;
+    int64_t  arrival_ms;        /* of its (first) packet */
+    uint32_t flags;             /* EDGPU_AAC_DISCONT ... */
+    uint32_t first_seq;
+    uint32_t n_packets;
+    uint32_t au_index;          /* its place among its packet's AUs */
+    uint32_t stream;            /* index of its edgpu_aac_stream row */
+    uint32_t _pad;
+} edgpu_aac_frame;
+typedef struct edgpu_aac_stream {   /* one enabled audio tap, in (session, track) order */
+    uint32_t session, track;
+    uint64_t offset;            /* 16-B aligned; the stream's frames follow each other from here */
+    uint64_t bytes;
+    uint32_t frame_first, frame_count;
+    /* cumulative since the tap was enabled */
+    uint64_t packets;           /* non-empty entries consumed */
+    uint64_t skipped, malformed, orphans, unsupported, missed;
+    uint64_t frames, discontinuities;   /* frames emitted; those with EDGPU_AAC_DISCONT */
+} edgpu_aac_stream;
+typedef struct edgpu_aac_result {
+    uint64_t bytes;             /* of `out` used (or needed) */
+    uint32_t frames, streams;   /* rows written (or needed) */
+} edgpu_aac_result;
+/* Reads the a=fmtp line of the SDP's `track`-th media section (0-based): mode=, sizelength,
+ * indexlength, indexdeltalength and config= (hex), keys matched case-insensitively.  Host only: no
+ * context, nothing is launched.  `out` gets the mode and the first 13 bits of the config; framing
+ * and frame_samples are left 0 (ADTS, 1024).  EDGPU_BAD_ARGUMENT: no such section or no fmtp line;
+ * a mode or lengths other than AAC-hbr with 13/3/3 or AAC-lbr with 6/2/2; a non-zero
+ * auxiliarydatasizelength, ctsdeltalength, dtsdeltalength, randomaccessindication or
+ * streamstateindication; a config shorter than 2 bytes; an object type, frequency index or channel
+ * count outside the ranges above. */
+int  edgpu_aac_config_parse(const char* sdp, uint32_t sdp_len, uint32_t track, edgpu_aac_config* out);
+/* Enables (or resets) the audio tap of `track`, from the next packet enqueued.  EDGPU_BAD_ARGUMENT
+ * unless the part of the track's payload name before its first '/' is "MPEG4-GENERIC" (compared
+ * case-insensitively) and `cfg` is in range.  The first enable allocates the context's audio-tap
+ * tables; each tap holds a work buffer sized from its sender's ring (again after the ring grows).
+ * Syncs. */
+int  edgpu_aac_tap_enable(edgpu_ctx* ctx, uint32_t session, uint32_t track, const edgpu_aac_config* cfg);
+/* Disables and clears it (no-op for a tap not enabled).  Syncs. */
+int  edgpu_aac_tap_disable(edgpu_ctx* ctx, uint32_t session, uint32_t track);
+/* Drains every enabled audio tap in one call, on the context stream, and syncs.  `out`, the host
+ * arrays and the pointer kinds are those of edgpu_tap_drain.  If the bytes, the frame rows or the
+ * stream rows do not fit, the call returns EDGPU_OUT_OVERFLOW, `result` holds the sizes needed and
+ * nothing is consumed: no head, counter or carried state changes, and a retry with room yields what
+ * a first call would have.  No byte of `out` outside [offset, roundup16(offset + bytes)) of some
+ * stream is written.  Its kernels' event pairs are edgpu_kernel_times(9). */
+int  edgpu_aac_tap_drain(edgpu_ctx* ctx, uint32_t flags, void* out, uint64_t out_cap, int ptr_kind,
+                         edgpu_aac_frame* frames, uint32_t frame_cap, edgpu_aac_stream* streams, uint32_t stream_cap,
+                         edgpu_aac_result* result);
+
 /* Per-launch device durations (ms, HIP events on the ctx stream) recorded since the last
  * call, oldest first, for `which` = 0 fan-out copy kernel, 1 whole fan-out tick (plan +
  * copy), 2 ingest (with the keyframe index it carries), 3 keyframe index (no entries since the
  * index runs inside the ingest kernel), 4 the stream-statistics kernel, 5 a tap drain's kernels,
- * 6 a transport-stream mux's kernels, 7 a fragmented-MP4 mux's kernels, 8 an FLV mux's kernels (4 to
- * 8 recorded only at EDGPU_TIMING_ALL).  Up to 256 launches are kept; the history is
+ * 6 a transport-stream mux's kernels, 7 a fragmented-MP4 mux's kernels, 8 an FLV mux's kernels, 9 an
+ * audio-tap drain's kernels (4 to 9 recorded only at EDGPU_TIMING_ALL).  Up to 256 launches are kept; the history is
  * cleared after reading.  Syncs. */
 int  edgpu_kernel_times(edgpu_ctx* ctx, int which, float* out_ms, uint32_t max_n, uint32_t* out_n);
 

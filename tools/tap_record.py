@@ -17,6 +17,12 @@ counts them in "stand_in_init".
 --flv records FLV (Context.tap_drain_flv, easydarwin_amd/flv.py): one video tag per access unit,
 muxed on the GPU, in <session>_<track>_<n>.flv behind the file header, onMetaData and the AVC sequence
 header, cut by the same rule; the stand-in parameter sets serve its headers in the same way.
+
+--audio also taps every MPEG4-GENERIC track (edgpu_aac_tap_*), with the config taken from its fmtp line,
+and records <session>_<track>_<n>.aac (ADTS) through easydarwin_amd/aac.py, listed in audio_index.json.
+The audio taps are flushed whenever --segment seconds have passed since the last flush, and at the end,
+so that aac.Recorder, which cuts a file only after a flush, cuts by the same period.
+The synthetic push then carries an RFC 3640 AAC-hbr track instead of PCMA.
 """
 import argparse
 import json
@@ -104,9 +110,9 @@ class StandInHeader:
             return edgpu.flv_header(STAND_IN_SPS, STAND_IN_PPS, timestamp_ms, parts)
 
 
-def synthetic(nsessions, seconds):
+def synthetic(nsessions, seconds, audio=False):
     tracks = [TrackSpec("video", "H264/90000", 96, bitrate=1_000_000, gop=30, idr_bytes=20_000),
-              TrackSpec("audio", "PCMA/8000", 8)]
+              TrackSpec("audio", "MPEG4-GENERIC/48000/2", 97, extra={"rfc3640": True}) if audio else TrackSpec("audio", "PCMA/8000", 8)]
     sdps = [make_sdp(tracks)] * nsessions
     pushes = [session_packets(tracks, seconds * 1000, SEED_BASE + i) for i in range(nsessions)]
     return sdps, pushes
@@ -133,11 +139,16 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--mp4", action="store_true", help="record fragmented MP4 instead of Annex-B")
     ap.add_argument("--flv", action="store_true", help="record FLV instead of Annex-B")
+    ap.add_argument("--audio", action="store_true", help="also record every MPEG4-GENERIC track as ADTS .aac")
     a = ap.parse_args()
     if a.mp4 and a.flv:
         ap.error("--mp4 and --flv exclude each other")
     os.makedirs(a.out, exist_ok=True)
-    sdps, pushes = from_trace(a.trace) if a.trace else synthetic(a.sessions, a.seconds)
+    sdps, pushes = from_trace(a.trace) if a.trace else synthetic(a.sessions, a.seconds, a.audio)
+    arec = None
+    if a.audio:
+        from easydarwin_amd import aac
+        arec = aac.Recorder(a.out, a.segment)
     if a.mp4:
         from easydarwin_amd import mp4
         init = StandInInit()
@@ -161,9 +172,17 @@ def main():
                 except edgpu.EdgpuError as e:
                     if e.code != edgpu.BAD_ARGUMENT:
                         raise                                       # (not an H.264 track)
+                if arec is None:
+                    continue
+                try:
+                    ctx.aac_tap_enable(s, t, edgpu.aac_config_parse(sdp, t))
+                except edgpu.EdgpuError as e:
+                    if e.code != edgpu.BAD_ARGUMENT:
+                        raise                                       # (no MPEG4-GENERIC track the tap supports)
         merged = sorted(((t, i, ch, d) for i, pk in enumerate(pushes) for t, ch, d in pk), key=lambda x: x[0])
         end = merged[-1][0] + 1 if merged else 0
         k = 0
+        flushed_at = 0
         for tick in range(0, end + a.tick_ms, a.tick_ms):
             batch = []
             while k < len(merged) and merged[k][0] < tick + a.tick_ms:
@@ -183,12 +202,21 @@ def main():
                 rec.push(data, tags, streams)
             else:
                 rec.take(*ctx.tap_drain(flush=tick + a.tick_ms > end))
+            if arec is not None:
+                last = tick + a.tick_ms > end or tick + a.tick_ms - flushed_at >= int(a.segment * 1000)
+                if last:
+                    flushed_at = tick + a.tick_ms
+                arec.push(*ctx.aac_tap_drain(flush=last), flushed=last)
     rec.close()
+    audio = {}
+    if arec is not None:
+        arec.close()
+        audio = {"audio_files": len(arec.files), "audio_frames": arec.frames}
     if a.mp4 or a.flv:
         print(json.dumps({"files": sum(len(v["files"]) for v in rec.summary().values()), "units": units,
-                          "streams": rec.summary(), "stand_in_init": init.count}))
+                          "streams": rec.summary(), "stand_in_init": init.count, **audio}))
     else:
-        print(json.dumps({"files": len(rec.files), "units": rec.drained_units}))
+        print(json.dumps({"files": len(rec.files), "units": rec.drained_units, **audio}))
 
 
 if __name__ == "__main__":
